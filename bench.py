@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark: spectrum points per second of the fused transit integrator on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps, writes the last step's R under --dump-outputs DIR if given, and
+prints the headline line (value, ms_per_step, the workload).  --full adds everything else the benchmark measures,
+each in runs of its own: the CPU baseline legs, the instrumented first run (stage times, chord counts), the tau
+kernel's sampled in-loop duration, per-kernel durations and rooflines, single-run latency, end-to-end calls, the
+strong-scaling projection and, for N > 1, the default strong legs.
 
 N=1: the largest single-GPU configuration of BASELINE.json, configs[2] (C3: power-law atmosphere
 with Na I + Ca II + Mg I, orbital Doppler shift on, 351,222 wavelengths x 16 orbital phases x
@@ -28,7 +34,7 @@ path (torch.distributed carries only the timing barrier and the max-over-ranks t
   --shard-axis phase: strong splits over orbital phases instead (every wavelength, phases [o0, o1)): the
       phases are independent too, and a phase shard does not repeat the per-phase chord work.
 
-The N=1 line also carries, per kernel of the step, its device duration (prom_transit_kernel_ms: one run in
+With --full the N=1 line also carries, per kernel of the step, its device duration (prom_transit_kernel_ms: one run in
 flight, dispatch-packet events) with its algorithmic bytes and roofline fraction, the path-level fraction
 (compulsory bytes / ms_per_step), a live HBM read peak, and the strong-scaling projection of the two
 8-GPU configurations (C4x10, C5): T(full grid) / T(shard 0 of 8), each timed on this GPU.
@@ -77,17 +83,26 @@ def parse():
                     help="strong splits (--shard, --scaling strong): contiguous wavelength ranges, orbital-phase "
                          "ranges (every wavelength, phases [o0, o1)), or auto (default): phases when every rank "
                          "gets the same number of them, else wavelengths")
-    ap.add_argument("--strong", default="C4x10,C4x10p256", metavar="CONFIGS",
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the CPU baseline legs, the instrumented first run, per-kernel "
+                         "durations and rooflines, single-run latency, end-to-end calls, the strong-scaling "
+                         "projection and (N > 1) the default strong legs -- each takes runs of its own")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (this rank's R) as DIR/<name>.npy "
+                         "in float64: R.npy whole, or above the size limit a fixed seeded sample of it (R.npy the "
+                         "values, R_index.npy their flat indices)")
+    ap.add_argument("--strong", default=None, metavar="CONFIGS",
                     help="N > 1: after the main leg, also time these configurations split over the N ranks in "
                          "contiguous wavelength shards (the north-star strong-scaling axis; the line's `strong` "
-                         "object, with each one's full grid timed on rank 0 alone for the speedup); '' to skip")
+                         "object, with each one's full grid timed on rank 0 alone for the speedup); '' to skip "
+                         "(default: C4x10,C4x10p256 with --full, else none)")
     ap.add_argument("--no-projection", action="store_true",
-                    help="skip the strong-scaling projection (C4x10 and C5, full grid vs shard 0 of 8)")
+                    help="--full: skip the strong-scaling projection (C4x10 and C5, full grid vs shard 0 of 8)")
     ap.add_argument("--kernel-runs", type=int, default=20,
-                    help="serialized runs for the per-kernel durations (prom_transit_kernel_ms)")
+                    help="--full: serialized runs for the per-kernel durations (prom_transit_kernel_ms)")
     ap.add_argument("--cpu-workers", type=int, default=None,
                     help="processes of the multi-core CPU baseline leg (default: this process's CPU share, <= 16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline legs")
     ap.add_argument("--dump-R", default=None, metavar="DIR",
                     help="after the timed loop, save this rank's R shard and its wavelength range under DIR "
                          "(tests: the gathered shards against a single-rank run)")
@@ -99,6 +114,10 @@ def parse():
         a.scaling = "weak"
     if a.config is None:
         a.config = "C4x10" if (world > 1 and a.scaling == "strong") else "C3"
+    if a.strong is None:
+        a.strong = "C4x10,C4x10p256" if a.full else ""
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps needs at least 1, --warmup at least 0")
     return a
 
 
@@ -293,6 +312,26 @@ def time_runs(dev, prob, steps: int, warmup: int) -> float:
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+DUMP_BYTES = 60_000_000   # --dump-outputs: all files of a run together (64 MB limit, with room for headers)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(out_dir: str, R: np.ndarray, rank: int, world: int) -> None:
+    """--dump-outputs: this rank's R of the last timed step ([phases, wavelengths], what prom_transit_result hands
+    a caller) as float64 .npy.  Whole when it fits the rank's share of DUMP_BYTES; else a fixed sample: flat indices
+    drawn once from a seeded generator (the same for every run of the same shape), sorted, saved beside the values."""
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "R" if world == 1 else "R_rank%d" % rank
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    budget = DUMP_BYTES // max(1, world)
+    if R.nbytes <= budget:
+        np.save(os.path.join(out_dir, tag + ".npy"), R)
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(R.size, size=budget // 16, replace=False))
+    np.save(os.path.join(out_dir, tag + ".npy"), R.reshape(-1)[idx])
+    np.save(os.path.join(out_dir, tag + "_index.npy"), idx.astype(np.float64))
+
+
 def strong_projection(dev_id: int, names=("C4x10", "C4x10p64", "C5"), parts: int = 8):
     """Strong scaling measured on one GPU: each configuration's full grid, then the largest
     of `parts` wavelength shards (edges on 256 wavelengths) and the largest of `parts` orbital-phase shards,
@@ -387,7 +426,7 @@ def main():
     args = parse()
     rank, local_rank, world = dist_env()
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.shard:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.shard:
         # before anything touches the GPU: the multi-core leg forks worker processes
         cfgc = global_config(args.config, 1)
         cfgc["_name"] = args.config
@@ -441,10 +480,13 @@ def main():
     dev.transit_set(prob)
     dev.transit_run()   # first launch of every kernel (code-object load) outside the stats run
     dev.synchronize()
-    st = dev.transit_run(stats=True)
+    # --full: the instrumented run (stage times, chord counts, evaluation counters)
+    st = dev.transit_run(stats=True) if args.full else None
     setup_s = time.perf_counter() - t_setup
     n_orb = len(host["orb"])
     n_pts_rank = (w1 - w0) * n_orb
+    n_pr = len(host["y"])
+    n_x = len(host["x"])
 
     have_torch_gpu = torch.cuda.is_available()
 
@@ -459,15 +501,18 @@ def main():
     if dist:
         dist.barrier()
     sync()
-    # the tau kernel's duration is sampled on every TAU_TIMING_STRIDE-th run (events on a dispatch cost
+    # --full: the tau kernel's duration is sampled on every TAU_TIMING_STRIDE-th run (events on a dispatch cost
     # the host ~13 us, more than a run's GPU time: timing every run would measure the host)
-    dev.timing_begin(stride=TAU_TIMING_STRIDE)
+    if args.full:
+        dev.timing_begin(stride=TAU_TIMING_STRIDE)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         dev.transit_run()
     sync()
     t1 = time.perf_counter()
-    ms_runs = dev.timing_end(max_runs=args.steps)
+    ms_runs = dev.timing_end(max_runs=args.steps) if args.full else np.zeros((0, 4))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dev.transit_result(), rank, world)
     if args.dump_R:
         os.makedirs(args.dump_R, exist_ok=True)
         np.save(os.path.join(args.dump_R, "R_rank%d.npy" % rank), dev.transit_result())
@@ -479,6 +524,58 @@ def main():
     elapsed, total_pts = sharding.reduce_timing(dist, t1 - t0, n_pts_rank)
     ms_step = elapsed / args.steps * 1e3
     value = total_pts * args.steps / elapsed
+
+    workload = "%s (%s), %d wavelengths x %d phases x %d chords x %d samples" % (
+        cfg_name, describe(cfg), n_wav_global, n_orb, n_pr, n_x)
+    if args.shard:
+        workload += (", shard %s: phases [%d, %d)" % (args.shard, o0, o1) if args.shard_axis == "phase"
+                     else ", shard %s: wavelengths [%d, %d)" % (args.shard, w0, w1))
+    elif world > 1:
+        workload += ", %s scaling over %ss: %d global phases x %d global wavelengths, rank 0 %s" % (
+            scaling, args.shard_axis, n_orb_global, n_wav_global,
+            "phases [%d, %d)" % (o0, o1) if args.shard_axis == "phase" else "wavelengths [%d, %d)" % (w0, w1))
+    result = {
+        "metric": "spectrum points/sec (phase x wavelength)",
+        "value": value,
+        "unit": "spectrum points/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (WASP-49b catalogue system, NIST line list bundled from the reference)",
+        "config": {"workload": workload,
+                   "global_wavelengths": n_wav_global, "orbital_phases": n_orb,
+                   "chords_per_phase": n_pr, "los_samples": n_x,
+                   "parallelism": "%s shards x%d (no collective)" % (
+                       "phase" if (args.shard_axis == "phase" and (args.shard or world > 1)) else "wavelength",
+                       world)},
+        "setup_s": setup_s,
+    }
+
+    def finish():
+        if dist and args.strong and not args.shard:
+            # (after the main leg; its problem is released first)
+            strong = {}
+            for name in [c for c in args.strong.split(",") if c]:
+                strong[name] = strong_leg(name, dev_id, dist, rank, world, args.steps, args.warmup,
+                                          os.path.join(args.dump_R, "strong_" + name) if args.dump_R else None)
+            result["strong"] = strong
+        if cpu is not None:
+            result["cpu_baseline"] = cpu
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result))
+
+    if not args.full:
+        # the plain run ends here: set up, warmed up, timed, outputs written
+        del tr, prob
+        return finish()
 
     # variant // 10: 3 planned tau kernel on sigma rows, 5 / 6 planned with the Doppler sigma fused in (exp10 /
     # polynomial lookups), 7 fused Doppler rows (k_sigma_poly integrates the light windows; k_tau_p takes the
@@ -506,8 +603,6 @@ def main():
     same_shift = all(np.all(np.asarray(e["shift"]) == np.asarray(e["shift"])[0]) for e in host["scenarios"])
     sigma_rows = 1 if same_shift else n_orb
     n_w = w1 - w0
-    n_pr = len(host["y"])
-    n_x = len(host["x"])
     merged = n_atoms == 1 and prob.n_atoms > 1
     peak_meas, peak_src = measured_read_peak()
 
@@ -630,34 +725,7 @@ def main():
     if world == 1 and not args.shard and not args.no_projection:
         del tr
         proj = strong_projection(dev_id)
-    workload = "%s (%s), %d wavelengths x %d phases x %d chords x %d samples" % (
-        cfg_name, describe(cfg), n_wav_global, n_orb, n_pr, n_x)
-    if args.shard:
-        workload += (", shard %s: phases [%d, %d)" % (args.shard, o0, o1) if args.shard_axis == "phase"
-                     else ", shard %s: wavelengths [%d, %d)" % (args.shard, w0, w1))
-    elif world > 1:
-        workload += ", %s scaling over %ss: %d global phases x %d global wavelengths, rank 0 %s" % (
-            scaling, args.shard_axis, n_orb_global, n_wav_global,
-            "phases [%d, %d)" % (o0, o1) if args.shard_axis == "phase" else "wavelengths [%d, %d)" % (w0, w1))
-    result = {
-        "metric": "spectrum points/sec (phase x wavelength)",
-        "value": value,
-        "unit": "spectrum points/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (WASP-49b catalogue system, NIST line list bundled from the reference)",
-        "config": {"workload": workload,
-                   "global_wavelengths": n_wav_global, "orbital_phases": n_orb,
-                   "chords_per_phase": n_pr, "los_samples": n_x,
-                   "parallelism": "%s shards x%d (no collective)" % (
-                       "phase" if (args.shard_axis == "phase" and (args.shard or world > 1)) else "wavelength",
-                       world)},
+    result.update({
         "roofline": {"bound": dk.get("bound", "hbm"), "kernel": dom, "achieved": dk.get("achieved"),
                      "peak": dk.get("peak", HBM_PEAK_GBS), "unit": dk.get("unit", "GB/s"), "frac": dk.get("frac"),
                      "traffic": traffic, "algorithmic_bytes": dk.get("algorithmic_bytes"),
@@ -674,27 +742,13 @@ def main():
         "single_run_ms": single_run_ms,
         "chords": {"active": st["active_chords"], "transparent": st["transparent_chords"],
                    "blocked": st["blocked_chords"], "integrated_records": st["tau_records"]},
-        "setup_s": setup_s,
         "end_to_end_s": e2e_s,
         "end_to_end_points_per_s": (n_wav_global * n_orb / e2e_s) if e2e_s else None,
-    }
+    })
     if proj is not None:
         result["strong_scaling_projection"] = proj
-    if dist and args.strong and not args.shard:
-        # (after the main leg; its problem is released first)
-        del prob
-        strong = {}
-        for name in [c for c in args.strong.split(",") if c]:
-            strong[name] = strong_leg(name, dev_id, dist, rank, world, args.steps, args.warmup,
-                                      os.path.join(args.dump_R, "strong_" + name) if args.dump_R else None)
-        result["strong"] = strong
-    if cpu is not None:
-        result["cpu_baseline"] = cpu
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(result))
+    del prob
+    finish()
 
 
 if __name__ == "__main__":

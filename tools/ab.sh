@@ -16,7 +16,7 @@ for c in ${CFGS:-C3}; do
   i=0
   for v in "$@"; do
     i=$((i+1))
-    env $v timeout -k 10 200 python -u bench.py --config $c --no-cpu-baseline --no-projection --steps ${STEPS:-200} --warmup 20 > "$O/bench_${c}_$i.log" 2>&1 \
+    env $v timeout -k 10 200 python -u bench.py --full --config $c --no-cpu-baseline --no-projection --steps ${STEPS:-200} --warmup 20 > "$O/bench_${c}_$i.log" 2>&1 \
       || { tail -5 "$O/bench_${c}_$i.log"; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$O/bench_${c}_$i.log').read().strip().splitlines()[-1])

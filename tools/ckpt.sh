@@ -24,7 +24,7 @@ fi
 for c in ${CFGS:-C3}; do
   if has bench; then
     extra=""; [ "$c" != C3 ] && extra="--no-cpu-baseline --no-projection"
-    timeout -k 10 600 python -u bench.py --config $c $extra > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 1; }
+    timeout -k 10 600 python -u bench.py --full --config $c $extra > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 1; }
     tail -1 $O/bench_$c.log > $O/bench_$c.json
     python3 -c "import json; d=json.load(open('$O/bench_$c.json')); print('$c', '%.4e' % d['value'], '%.4f ms' % d['ms_per_step'], d['roofline']['kernel'], '%.3f' % (d['roofline']['frac'] or 0))"
   fi

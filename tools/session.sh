@@ -21,12 +21,12 @@ if has smoke; then
   tail -1 $O/smoke.log | cut -c1-300
 fi
 if has bench; then
-  timeout -k 10 400 python -u bench.py --config $CFG > $O/bench_$CFG.log 2>&1 || { tail -20 $O/bench_$CFG.log; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --config $CFG > $O/bench_$CFG.log 2>&1 || { tail -20 $O/bench_$CFG.log; exit 1; }
   tail -1 $O/bench_$CFG.log | cut -c1-600
 fi
 if has extra; then
   for c in ${CONFIGS:-C2 C4}; do
-    timeout -k 10 300 python -u bench.py --config $c --no-cpu-baseline --steps 100 --warmup 10 > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 1; }
+    timeout -k 10 300 python -u bench.py --full --config $c --no-cpu-baseline --steps 100 --warmup 10 > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 1; }
     tail -1 $O/bench_$c.log | cut -c1-300
   done
 fi
