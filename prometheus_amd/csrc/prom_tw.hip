@@ -1,5 +1,6 @@
 // k_sigma_tw: the Doppler-shifted cross-section lookups and transmission curves over target windows.
 #include "prom_tc.h"
+#include "tw_index.h"
 
 namespace prom {
 
@@ -135,7 +136,6 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
     }
     double cdv = pc.c[D];
     asm volatile("" : "+v"(cdv));
-    const double* lamb = slam + lane - lw0;   // (the staged wavelengths, this lane's column; 64 entries of padding)
     // NP points per lane at once: rows a and b (RP = 2: a row pair, the two rows' chunks k side by side -- two
     // independent lookup chains per lane), with each row's Doppler factor, header, table and R row in scalar registers
     struct RowS {
@@ -165,8 +165,11 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
 #pragma unroll
       for (int p = 0; p < NP; ++p) t[p] = rs[p].sh * lam[p];
       // every species' x_g (x_{g+1}) and record in one LDS round, then, unless every guess is exact, the rare
-      // one-node corrections, then the e^a polynomials.  (The guess clamps at m - 2 only: every target of the
-      // window lies in the slice, so fma(t, inv, xs) > -1 and the integer conversion is >= 0, as seg_guess's)
+      // one-node corrections, then the e^a polynomials.  (tw_guess clamps at m - 2 only: the dispatch below computes
+      // chunks of rows with wavelengths in the window only, every wavelength a lane reads is one of its row's or a
+      // later one, and every target of the row lies in the slice, so fma(t, inv, xs) > -1 and the guess is >= 0.
+      // Lanes past the row's end that fall into the stage's 64 entries of padding hold no wavelength at all: whatever
+      // they look up, they store nothing)
       int32_t g[NP][NSIG];
       double x0[NP][NSIG], x1[NP][NSIG];
       double2 e[NP][NSIG];
@@ -174,7 +177,7 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
       for (int p = 0; p < NP; ++p)
 #pragma unroll
         for (int s = 0; s < NSIG; ++s) {
-          g[p][s] = min((int32_t)__builtin_fma(t[p], sg[s].inv, xsv[s]), sg[s].m - 2);
+          g[p][s] = tw_guess(t[p], sg[s].inv, xsv[s], sg[s].m);
           x0[p][s] = xsb[s][g[p][s]];
           if constexpr (!EX) x1[p][s] = xsb[s][g[p][s] + 1];
           e[p][s] = elb[s][g[p][s]];
@@ -224,21 +227,21 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
     };
     // the NP rows' chunks k = k0, k0 + G, ...: the wavelengths from the LDS stage, else loaded up to four chunks at a
     // time before any of them is computed (one vmcnt wait -- which also waits for the earlier stores -- per batch).  A
-    // row with fewer chunks than its partner computes a clamped chunk and stores nothing
+    // row with fewer chunks than its partner computes a clamped chunk (tw_chunk_read: its first) and stores nothing;
+    // every row here has w0 < w1 (tw_index.h)
     auto rows = [&](const RowS* rs, auto np_tag, int32_t k0, int32_t G, auto mode_tag) {
       constexpr int NP = decltype(np_tag)::value;
       int32_t nch = 0;
 #pragma unroll
-      for (int p = 0; p < NP; ++p) nch = max(nch, (rs[p].w1 - rs[p].w0 + 63) >> 6);
-      auto cfix = [&](int p, int32_t c) { return c < rs[p].w1 ? c : rs[p].w0; };   // (a clamped, computed chunk)
+      for (int p = 0; p < NP; ++p) nch = max(nch, tw_chunks(rs[p].w0, rs[p].w1));
       if (nlam > 0) {
         for (int32_t k = k0; k < nch; k += G) {
           int32_t c0[NP];
           double lam[NP];
 #pragma unroll
           for (int p = 0; p < NP; ++p) {
-            c0[p] = rs[p].w0 + 64 * k;
-            lam[p] = lamb[cfix(p, c0[p])];
+            c0[p] = tw_chunk_first(rs[p].w0, k);
+            lam[p] = slam[tw_lam_staged(rs[p].w0, rs[p].w1, k, lane, lw0)];
           }
           chunk(rs, np_tag, c0, lam, mode_tag);
         }
@@ -249,16 +252,13 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
 #pragma unroll
           for (int j = 0; j < B; ++j)
 #pragma unroll
-            for (int p = 0; p < NP; ++p) {
-              const int32_t w = cfix(p, rs[p].w0 + 64 * (k + j * G)) + lane;
-              lam[j][p] = wav[w < rs[p].w1 ? w : rs[p].w1 - 1];
-            }
+            for (int p = 0; p < NP; ++p) lam[j][p] = wav[tw_lam_global(rs[p].w0, rs[p].w1, k + j * G, lane)];
 #pragma unroll
           for (int j = 0; j < B; ++j) {
             if (k + j * G >= nch) break;
             int32_t c0[NP];
 #pragma unroll
-            for (int p = 0; p < NP; ++p) c0[p] = rs[p].w0 + 64 * (k + j * G);
+            for (int p = 0; p < NP; ++p) c0[p] = tw_chunk_first(rs[p].w0, k + j * G);
             chunk(rs, np_tag, c0, lam[j], mode_tag);
           }
         }
@@ -271,7 +271,7 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
     };
     auto rare_row = [&](int32_t o) { return ((int32_t)hdr[(int64_t)o * kTcHdr + kTcHFlags] & 6) != 0; };
     if constexpr (RP == 1) {
-      const int32_t G = n_rows >= 4 ? 1 : (n_rows == 1 ? 4 : 2);   // waves per row
+      const int32_t G = tw_waves_per_unit(n_rows);   // waves per row
       for (int32_t o = __builtin_amdgcn_readfirstlane(wv / G); o < n_rows; o += 4 / G) {
         if (rare_row(o)) continue;   // (second pass)
         const RowS r1[1] = {row_of(o)};
@@ -279,17 +279,20 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
       }
     } else {
       // row pairs (2q, 2q + 1) round robin over the waves (G waves per pair when there are fewer than 4 pairs); a pair
-      // with one row in the second pass (or past n_rows) runs its other row alone
+      // with one row absent (in the second pass, past n_rows or without wavelengths in this window) runs its other
+      // row alone, a pair of two absent rows nothing: no chunk of an empty row is ever computed
       const int32_t P = (n_rows + 1) >> 1;
-      const int32_t G = P >= 4 ? 1 : (P == 1 ? 4 : 2);
+      const int32_t G = tw_waves_per_unit(P);
       for (int32_t q = __builtin_amdgcn_readfirstlane(wv / G); q < P; q += 4 / G) {
         const int32_t oa = 2 * q, ob = 2 * q + 1;
-        const bool ra = rare_row(oa), rb = ob >= n_rows || rare_row(ob);
-        if (!ra && !rb) {
+        const bool ra = tw_row_absent(rare_row(oa), wa[oa], wz[oa]);
+        const bool rb = ob >= n_rows || tw_row_absent(rare_row(ob), wa[ob], wz[ob]);
+        const int32_t pr = tw_pair_rows(ra, rb);
+        if (pr == 3) {
           const RowS r2[2] = {row_of(oa), row_of(ob)};
           rows_mode(r2, std::integral_constant<int, 2>{}, wv % G, G);
-        } else if (!ra || !rb) {
-          const RowS r1[1] = {row_of(ra ? ob : oa)};
+        } else if (pr != 0) {
+          const RowS r1[1] = {row_of(pr == 1 ? oa : ob)};
           rows_mode(r1, std::integral_constant<int, 1>{}, wv % G, G);
         }
       }
