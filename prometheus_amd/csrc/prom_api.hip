@@ -11,6 +11,7 @@
 #include <thread>
 
 #include "prom_internal.h"
+#include "tw_stage.h"
 
 using prom::DevBuf;
 using prom::Error;
@@ -946,7 +947,12 @@ int32_t prom_transit_set(prom_ctx* ctx, const prom_transit_problem* pb) {
           return;
         stg.add(tr.tw_seg, twseg.data(), (int64_t)twseg.size(), s);
         stg.add(tr.tw_row, twrow.data(), (int64_t)twrow.size(), s);
-        stg.add(tr.tw_lam, twlam.data(), (int64_t)twlam.size(), s);
+        // the windows' stage records (tw_stage.h), from the finished plan; k_tw_exact marks them with the slices
+        std::vector<prom::TwStage> twstg((size_t)nw);
+        for (int32_t b = 0; b < nw; ++b)
+          twstg[b] = prom::tw_stage_of(twseg.data() + (int64_t)b * (int64_t)tabs.size(), (int32_t)tabs.size(), twlam[2 * b],
+                                       twlam[2 * b + 1]);
+        stg.add(tr.tw_stage, twstg.data(), (int64_t)twstg.size(), s);
         tr.n_tw = nw;
         tr.tw_ok = true;
         tr.tw_new = true;

@@ -384,7 +384,7 @@ struct TransitDev {
   // per window boundary and row the first wavelength; built with the sigma segments (same inputs, same reuse)
   DevBuf tw_seg;                            // [n_tw][n_atoms] SigSeg
   DevBuf tw_row;                            // [n_tw + 1][n_orb] int32
-  DevBuf tw_lam;                            // [n_tw][2] int32: the wavelengths [lw0, lw1) staged per window (lw1 = lw0: none)
+  DevBuf tw_stage;                          // [n_tw] TwStage (tw_stage.h): the window's stage record, its staged wavelengths with it
   int32_t n_tw = 0;
   bool tw_ok = false;
   bool tw_new = false;                      // (built by this set: the exact marks are still to come)

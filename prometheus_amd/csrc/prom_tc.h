@@ -111,25 +111,39 @@ __device__ __forceinline__ double fma_s(double a, double b, double c) {
   return r;
 }
 
-// tc_eval_full with the row's header in scalar registers (h uniform): the tail polynomial by fma_s, the rest as
-// tc_eval_full (the same operations in the same order: bitwise its result)
-__device__ __forceinline__ double tc_eval_full_s(double Y, const double* __restrict__ h, const double* __restrict__ tabo) {
-  const double q = Y * h[kTcHNmax];
-  const double tf = h[kTcHTfrac];
+// A row's curve scalars held for all its chunks (k_sigma_tw's first pass): what the q < eps path reads, loaded once
+// per row in one batch of scalar loads -- N_max, tfrac and the tail coefficients t_0 .. t_4 in scalar registers, the
+// leading coefficient t_5 in a vector pair (fma_s) -- so that path loads nothing per chunk; the rare branches read
+// the header h as tc_eval_full does
+struct TcRow {
+  const double* h;
+  const double* tabo;
+  double nmax, tf, t[5];
+  double t5v;
+};
+
+// the header's flags say second pass (2: non-finite columns, 4: truncated at the octave cap), from the double's
+// bits: the flags are the double of an integer 0 .. 7, so (flags & 6) != 0 is flags >= 2.0, a compare of its high
+// word -- scalar, where the conversion to an integer is a vector instruction and a round trip through a lane
+__device__ __forceinline__ bool tc_flags_second_pass(double flags) {
+  return (int32_t)(__builtin_bit_cast(unsigned long long, flags) >> 32) >= 0x40000000;
+}
+
+// tc_eval_full on a TcRow (the tail polynomial by fma_s: the same operations in the same order, bitwise its result)
+__device__ __forceinline__ double tc_eval_full_r(double Y, const TcRow& r) {
+  const double q = Y * r.nmax;
   if (q < kTcEps) {
-    double c5 = h[kTcHT0 + 5];
-    asm volatile("" : "+v"(c5));   // (the leading coefficient in VGPRs: one FMA may read one scalar pair)
-    double p = fma_s(c5, q, h[kTcHT0 + 4]);
+    double p = fma_s(r.t5v, q, r.t[4]);
 #pragma unroll
-    for (int e = 3; e >= 0; --e) p = fma_s(p, q, h[kTcHT0 + e]);
-    return tf + p;
+    for (int e = 3; e >= 0; --e) p = fma_s(p, q, r.t[e]);
+    return r.tf + p;
   }
-  const int32_t nact = (int32_t)h[kTcHNact];
-  if (!(q == q)) return nact > 0 ? q : tf;
-  const int32_t L = (int32_t)h[kTcHL];
+  const int32_t nact = (int32_t)r.h[kTcHNact];
+  if (!(q == q)) return nact > 0 ? q : r.tf;
+  const int32_t L = (int32_t)r.h[kTcHL];
   const int32_t j = q <= 1.0e300 ? tc_exponent(q) - kTcExpEps : 0x7fffffff;
-  if (j >= L) return tf;
-  return tf + tc_clenshaw(q, tabo + (int64_t)j * kTcD);
+  if (j >= L) return r.tf;
+  return r.tf + tc_clenshaw(q, r.tabo + (int64_t)j * kTcD);
 }
 
 // tc_eval for a phase whose table covers every q it can reach (curve header flag 4 clear: not truncated at the

@@ -1,6 +1,7 @@
 // k_sigma_tw: the Doppler-shifted cross-section lookups and transmission curves over target windows.
 #include "prom_tc.h"
 #include "tw_index.h"
+#include "tw_stage.h"
 
 namespace prom {
 
@@ -22,12 +23,16 @@ namespace prom {
 // octave cap (flag 4, the exact sum beyond it): numpy's bracket from the table's directory, per point.  Every path
 // evaluates fl(chi E_k) e^a (or E_k e^a - offset) of numpy's bracket k, so R does not depend on the windows: bitwise
 // equal to k_sigma_tc's and for any wavelength or phase shard.
+// What a wave needs before its first chunk is kept short: the staging reads the window's stage record (tw_stage.h,
+// derived per set from the plan: one scalar load instead of a classification of every pool entry against every
+// slice), a row's curve scalars are one batch of scalar loads held for all its chunks (TcRow, prom_tc.h), and the
+// first pass is split outermost by wavelength source, so the staged instance's loops wait for no vector memory.
 
 template <int NSIG, int D, bool MG, int RP>
 __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const SigTabDev* __restrict__ tabp,
                                                      const PolyCoef pc, const double* __restrict__ wav,
                                                      int64_t n_wav, int32_t n_rows, const SigSeg* __restrict__ wseg,
-                                                     const int32_t* __restrict__ wrow, const int32_t* __restrict__ wlam,
+                                                     const int32_t* __restrict__ wrow, const TwStage* __restrict__ wstg,
                                                      int32_t n_win, const TcArgs ta,
                                                      const double* __restrict__ hdr, const double* __restrict__ shift,
                                                      const double* __restrict__ ctab, double* __restrict__ Rout) {
@@ -35,7 +40,7 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
   // stores provably elsewhere, the row's header and Doppler factor become scalar loads)
   static_assert(D > 0, "polynomial lookups only (coarse tables take k_sigma_tc)");
   // LDS: [0, 2 tot) the records {(chi) E_k, L_k} (species s at 2 pad), then tot + NSIG node x's (species s at pad + s:
-  // x_lo .. x_{lo+m}), then the window's wavelengths
+  // x_lo .. x_{lo+m}), then the window's wavelengths (tw_stage.h: tw_lds_x, tw_lds_lam)
   __shared__ double2 lds2[kTwLds / 2 + 32];   // (+ 64 doubles: the staged wavelengths' padding, read past lw1)
   double* const lds = reinterpret_cast<double*>(lds2);
   // XCD-aware: workgroup ids round-robin over the 8 XCDs; XCD x takes windows [x per, (x + 1) per) in order, so
@@ -45,63 +50,70 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
   if (b >= n_win) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the window's stage record (tw_stage.h: one scalar load) and, for the first pass' guesses, its slices
+  const TwStage st = wstg[b];
   SigSeg sg[NSIG];
-  bool wrare = false;   // (some species without a slice: second pass for the whole window)
-  bool wexact = true;   // (every guess is numpy's bracket at every target of the window: k_tw_exact, kind & 4)
-  bool wsearch = false; // (some staged slice without a guess, kind 3: bisection in LDS)
-  int32_t tot = 0;      // staged nodes (kinds 1 and 3)
 #pragma unroll
-  for (int s = 0; s < NSIG; ++s) {
-    sg[s] = wseg[(int64_t)b * NSIG + s];
-    wrare = wrare || ((sg[s].kind & 3) != 1 && (sg[s].kind & 3) != 3);
-    wsearch = wsearch || (sg[s].kind & 3) == 3;
-    wexact = wexact && (sg[s].kind & 4) != 0;
-    if (sg[s].kind & 1) tot = sg[s].pad + sg[s].m > tot ? sg[s].pad + sg[s].m : tot;
-  }
-  const int32_t lw0 = wlam[2 * b], nlam = wlam[2 * b + 1] - lw0;   // (nlam = 0: wavelengths from global memory)
+  for (int s = 0; s < NSIG; ++s) sg[s] = wseg[(int64_t)b * NSIG + s];
+  const bool wrare = (st.mode & kTwRare) != 0;      // (some species without a slice: second pass for the whole window)
+  const bool wexact = (st.mode & kTwExact) != 0;    // (every guess is numpy's bracket at every target: k_tw_exact)
+  const bool wsearch = (st.mode & kTwSearch) != 0;  // (some staged slice without a guess, kind 3: bisection in LDS)
+  const int32_t tot = st.tot;                       // staged nodes (kinds 1 and 3)
+  const int32_t lw0 = st.lw0, nlam = st.nlam;       // (nlam = 0: wavelengths from global memory)
   double2* const sel = lds2;
-  double* const sx = lds + 2 * tot;
-  double* const slam = sx + tot + NSIG;
-  // stage the slices (pool entry i belongs to the species whose [pad, pad + m) holds it) and the wavelengths; every
-  // load issued before the first LDS write
+  double* const slam = lds + tw_lds_lam(tot, NSIG);
+  // stage the slices and the wavelengths; every load issued before the first LDS write, none behind a test: a
+  // thread past the pool's (the wavelengths') end loads entry 0 (the first wavelength) again and writes nothing, so
+  // the loads stay one batch with one wait.  Pool entry i belongs to species #{s : bnd[s] <= i}: one classification
+  // per entry, then its record base and abundance by selects -- from VGPR copies made once per thread (a select
+  // takes no scalar operand beside its mask: each would be copied again per entry)
   {
     constexpr int NQ = (kTwLds / 3 + kBlock - 1) / kBlock;
     constexpr int NL = (kTwLamCap + kBlock - 1) / kBlock;
+    const double4* recv[NSIG];   // species s' record of pool entry 0
+    double chiv[NSIG];
+#pragma unroll
+    for (int s = 0; s < NSIG; ++s) {
+      recv[s] = tabv.t[s].rec + st.off[s];
+      chiv[s] = MG ? tabv.t[s].chi : 1.0;
+      if constexpr (NSIG > 1) asm volatile("" : "+v"(recv[s]), "+v"(chiv[s]));
+    }
     double lq[NL];
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
       const int32_t i = tid + j * kBlock;
-      lq[j] = i < nlam ? wav[lw0 + i] : 0.0;
+      lq[j] = (wav + lw0)[(uint32_t)(i < nlam ? i : 0)];
     }
     double4 q[NQ];
-    int sp[NQ];
+    int32_t sp[NQ];
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
       const int32_t i = tid + j * kBlock;
-      sp[j] = -1;
+      const uint32_t iq = i < tot ? i : 0;
+      sp[j] = tw_stage_species(st.bnd, NSIG, (int32_t)iq);
+      const double4* rr = recv[0];
 #pragma unroll
-      for (int s = 0; s < NSIG; ++s)
-        if ((sg[s].kind & 1) && i >= sg[s].pad && i < sg[s].pad + sg[s].m) sp[j] = s;
-      int32_t gi = 0;
-      const double4* __restrict__ rr = tabv.t[0].rec;
-#pragma unroll
-      for (int s = 0; s < NSIG; ++s)
-        if (sp[j] == s) {
-          gi = sg[s].lo + (i - sg[s].pad);
-          rr = tabv.t[s].rec;
-        }
-      q[j] = i < tot ? rr[gi] : make_double4(0.0, 0.0, 0.0, 0.0);
+      for (int s = 1; s < NSIG; ++s) rr = sp[j] == s ? recv[s] : rr;
+      q[j] = rr[iq];
     }
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
       const int32_t i = tid + j * kBlock;
+      if (i >= tot) continue;
+      double e = q[j].y;
+      if constexpr (MG) {
+        double chi = chiv[0];
 #pragma unroll
-      for (int s = 0; s < NSIG; ++s) {
-        if (sp[j] != s) continue;
-        sx[i + s] = q[j].x;
-        sel[i] = make_double2(MG ? tabv.t[s].chi * q[j].y : q[j].y, q[j].z);
-        if (i == sg[s].pad + sg[s].m - 1) sx[i + s + 1] = q[j].w;   // the slice's last upper node
+        for (int s = 1; s < NSIG; ++s) chi = sp[j] == s ? chiv[s] : chi;
+        e = chi * e;
       }
+      // x_i and the upper node x_{i+1} after it: the slot of the species' next entry, which writes the same bits
+      // (a record's upper node is the next record's node), or after its last entry the slice's last upper node
+      double* const xi = lds + tw_lds_x(tot, i, sp[j]);
+      xi[0] = q[j].x;
+      xi[1] = q[j].w;
+      lds[2 * i] = e;
+      lds[2 * i + 1] = q[j].z;
     }
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
@@ -122,37 +134,56 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
   // loaded once into scalar registers, then the rows' chunks of 64 wavelengths
   if (!wrare) {
     // per species, hoisted by hand (the compiler keeps them as per-lookup arithmetic otherwise): the slice's LDS
-    // bases (lookup address = g * 8 + base), and the guess's offset and the polynomial's leading coefficient held in
-    // VGPRs (a 64-bit FMA takes one scalar operand: either would be copied to VGPRs before every use)
+    // bases from the stage record (lookup address = g * 8 + base), and the guess's offset and the polynomial's leading
+    // coefficient held in VGPRs (a 64-bit FMA takes one scalar operand: either would be copied to VGPRs before every use)
     const double* xsb[NSIG];
     const double2* elb[NSIG];
     double xsv[NSIG];
 #pragma unroll
     for (int s = 0; s < NSIG; ++s) {
-      xsb[s] = sx + sg[s].pad + s;
-      elb[s] = sel + sg[s].pad;
+      xsb[s] = lds + tw_stage_xbase(st.base[s]);
+      elb[s] = sel + tw_stage_elbase(st.base[s]);
       xsv[s] = sg[s].xs;
       asm volatile("" : "+v"(xsv[s]));
     }
     double cdv = pc.c[D];
     asm volatile("" : "+v"(cdv));
+    int32_t lg = ta.lg;   // (held from here: left to the compiler, the arguments are loaded again for every row)
+    int64_t rstride = n_wav;
+    asm volatile("" : "+s"(lg), "+s"(rstride));
     // NP points per lane at once: rows a and b (RP = 2: a row pair, the two rows' chunks k side by side -- two
-    // independent lookup chains per lane), with each row's Doppler factor, header, table and R row in scalar registers
+    // independent lookup chains per lane), with each row's Doppler factor, curve scalars, table and R row in scalar
+    // registers for all its chunks
     struct RowS {
-      const double* h;
-      const double* tabo;
+      TcRow c;
       double* Rrow;
       double sh;
       int32_t w0, w1;
+      bool rare;   // (header flags 2 or 4: the second pass takes the row)
     };
+    // one batch of scalar loads per row -- the header's flags, N_max, tfrac and tail coefficients, the Doppler factor
+    // and the row's wavelength range, none behind a test of another -- and one wait: the empty asm takes them all,
+    // so the loads stay together ahead of the second-pass test and the chunks reload none of them
     auto row_of = [&](int32_t o) {
       RowS r;
-      r.h = hdr + (int64_t)o * kTcHdr;
-      r.tabo = ctab + (int64_t)o * ta.lg * kTcD;
-      r.Rrow = Rout + (int64_t)o * n_wav + lane;   // (this lane's column of the row)
+      const double* __restrict__ h = hdr + (int64_t)o * kTcHdr;
+      r.c.h = h;
+      r.c.tabo = ctab + (int64_t)o * lg * kTcD;
+      r.c.nmax = h[kTcHNmax];
+      r.c.tf = h[kTcHTfrac];
+#pragma unroll
+      for (int e = 0; e < 5; ++e) r.c.t[e] = h[kTcHT0 + e];
+      double t5 = h[kTcHT0 + 5], fl = h[kTcHFlags];
       r.sh = shift[o];
       r.w0 = wa[o];
       r.w1 = wz[o];
+      asm volatile(""
+                   : "+s"(r.c.nmax), "+s"(r.c.tf), "+s"(r.c.t[0]), "+s"(r.c.t[1]), "+s"(r.c.t[2]), "+s"(r.c.t[3]),
+                     "+s"(r.c.t[4]), "+s"(t5), "+s"(fl), "+s"(r.sh), "+s"(r.w0), "+s"(r.w1));
+      r.rare = tc_flags_second_pass(fl);
+      r.c.t5v = t5;
+      asm volatile("" : "+v"(r.c.t5v));   // (the leading coefficient in VGPRs: one FMA may read one scalar pair)
+      r.Rrow = Rout + (int64_t)o * rstride + lane;   // (this lane's column of the row)
       return r;
     };
     // MODE 0: every guess exact; 1: guesses with the one-node test; 2: as 1, kind-3 slices by bisection.  c0[p]: the
@@ -190,8 +221,8 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
             if (MODE == 2 && (sg[s].kind & 3) == 3) {
               // numpy's bracket, the largest k <= m - 2 with x_k <= t, by bisection over the staged slice
               int32_t k = 0;
-              for (int32_t st = 1 << (31 - __builtin_clz((uint32_t)(sg[s].m - 1) | 1u)); st > 0; st >>= 1)
-                if (k + st <= sg[s].m - 2 && xsb[s][k + st] <= t[p]) k += st;
+              for (int32_t st2 = 1 << (31 - __builtin_clz((uint32_t)(sg[s].m - 1) | 1u)); st2 > 0; st2 >>= 1)
+                if (k + st2 <= sg[s].m - 2 && xsb[s][k + st2] <= t[p]) k += st2;
               x0[p][s] = xsb[s][k];
               e[p][s] = elb[s][k];
               continue;
@@ -221,20 +252,21 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
       }
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
-        const double v = tc_eval_full_s(acc[p], rs[p].h, rs[p].tabo);
+        const double v = tc_eval_full_r(acc[p], rs[p].c);
         if (c0[p] + lane < rs[p].w1) rs[p].Rrow[c0[p]] = v;
       }
     };
-    // the NP rows' chunks k = k0, k0 + G, ...: the wavelengths from the LDS stage, else loaded up to four chunks at a
-    // time before any of them is computed (one vmcnt wait -- which also waits for the earlier stores -- per batch).  A
+    // the NP rows' chunks k = k0, k0 + G, ...: the wavelengths from the LDS stage (STAGED: no vector load in the row
+    // and chunk loops, so no wait in them for the earlier stores either), else loaded up to four chunks at a time
+    // before any of them is computed (one vmcnt wait -- which also waits for the earlier stores -- per batch).  A
     // row with fewer chunks than its partner computes a clamped chunk (tw_chunk_read: its first) and stores nothing;
     // every row here has w0 < w1 (tw_index.h)
-    auto rows = [&](const RowS* rs, auto np_tag, int32_t k0, int32_t G, auto mode_tag) {
+    auto rows = [&](const RowS* rs, auto np_tag, int32_t k0, int32_t G, auto mode_tag, auto staged_tag) {
       constexpr int NP = decltype(np_tag)::value;
       int32_t nch = 0;
 #pragma unroll
       for (int p = 0; p < NP; ++p) nch = max(nch, tw_chunks(rs[p].w0, rs[p].w1));
-      if (nlam > 0) {
+      if constexpr (decltype(staged_tag)::value) {
         for (int32_t k = k0; k < nch; k += G) {
           int32_t c0[NP];
           double lam[NP];
@@ -264,39 +296,44 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
         }
       }
     };
-    auto rows_mode = [&](const RowS* rs, auto np_tag, int32_t k0, int32_t G) {
-      if (wexact) rows(rs, np_tag, k0, G, std::integral_constant<int, 0>{});
-      else if (!wsearch) rows(rs, np_tag, k0, G, std::integral_constant<int, 1>{});
-      else rows(rs, np_tag, k0, G, std::integral_constant<int, 2>{});
-    };
-    auto rare_row = [&](int32_t o) { return ((int32_t)hdr[(int64_t)o * kTcHdr + kTcHFlags] & 6) != 0; };
-    if constexpr (RP == 1) {
-      const int32_t G = tw_waves_per_unit(n_rows);   // waves per row
-      for (int32_t o = __builtin_amdgcn_readfirstlane(wv / G); o < n_rows; o += 4 / G) {
-        if (rare_row(o)) continue;   // (second pass)
-        const RowS r1[1] = {row_of(o)};
-        rows_mode(r1, std::integral_constant<int, 1>{}, wv % G, G);
-      }
-    } else {
-      // row pairs (2q, 2q + 1) round robin over the waves (G waves per pair when there are fewer than 4 pairs); a pair
-      // with one row absent (in the second pass, past n_rows or without wavelengths in this window) runs its other
-      // row alone, a pair of two absent rows nothing: no chunk of an empty row is ever computed
-      const int32_t P = (n_rows + 1) >> 1;
-      const int32_t G = tw_waves_per_unit(P);
-      for (int32_t q = __builtin_amdgcn_readfirstlane(wv / G); q < P; q += 4 / G) {
-        const int32_t oa = 2 * q, ob = 2 * q + 1;
-        const bool ra = tw_row_absent(rare_row(oa), wa[oa], wz[oa]);
-        const bool rb = ob >= n_rows || tw_row_absent(rare_row(ob), wa[ob], wz[ob]);
-        const int32_t pr = tw_pair_rows(ra, rb);
-        if (pr == 3) {
-          const RowS r2[2] = {row_of(oa), row_of(ob)};
-          rows_mode(r2, std::integral_constant<int, 2>{}, wv % G, G);
-        } else if (pr != 0) {
-          const RowS r1[1] = {row_of(pr == 1 ? oa : ob)};
+    // the pass for one wavelength source: the split is outermost, so the staged instance's row loop is its own code
+    auto first_pass = [&](auto staged_tag) {
+      auto rows_mode = [&](const RowS* rs, auto np_tag, int32_t k0, int32_t G) {
+        if (wexact) rows(rs, np_tag, k0, G, std::integral_constant<int, 0>{}, staged_tag);
+        else if (!wsearch) rows(rs, np_tag, k0, G, std::integral_constant<int, 1>{}, staged_tag);
+        else rows(rs, np_tag, k0, G, std::integral_constant<int, 2>{}, staged_tag);
+      };
+      if constexpr (RP == 1) {
+        const int32_t G = tw_waves_per_unit(n_rows);   // waves per row
+        for (int32_t o = __builtin_amdgcn_readfirstlane(wv / G); o < n_rows; o += 4 / G) {
+          const RowS r1[1] = {row_of(o)};
+          if (r1[0].rare) continue;   // (second pass)
           rows_mode(r1, std::integral_constant<int, 1>{}, wv % G, G);
         }
+      } else {
+        // row pairs (2q, 2q + 1) round robin over the waves (G waves per pair when there are fewer than 4 pairs); a
+        // pair with one row absent (in the second pass, past n_rows or without wavelengths in this window) runs its
+        // other row alone, a pair of two absent rows nothing: no chunk of an empty row is ever computed
+        const int32_t P = (n_rows + 1) >> 1;
+        const int32_t G = tw_waves_per_unit(P);
+        for (int32_t q = __builtin_amdgcn_readfirstlane(wv / G); q < P; q += 4 / G) {
+          const int32_t oa = 2 * q, ob = 2 * q + 1;
+          const RowS a = row_of(oa), z = row_of(ob < n_rows ? ob : oa);   // (past the last row: loaded from oa, absent)
+          const bool ra = tw_row_absent(a.rare, a.w0, a.w1);
+          const bool rb = ob >= n_rows || tw_row_absent(z.rare, z.w0, z.w1);
+          const int32_t pr = tw_pair_rows(ra, rb);
+          if (pr == 3) {
+            const RowS r2[2] = {a, z};
+            rows_mode(r2, std::integral_constant<int, 2>{}, wv % G, G);
+          } else if (pr != 0) {
+            const RowS r1[1] = {pr == 1 ? a : z};
+            rows_mode(r1, std::integral_constant<int, 1>{}, wv % G, G);
+          }
+        }
       }
-    }
+    };
+    if (nlam > 0) first_pass(std::true_type{});
+    else first_pass(std::false_type{});
   }
   // second pass: the rest (kinds 0, 2, 3, rows with header flags 2 or 4), numpy's bracket per
   // point from the table's directory; items (row o, chunk c of 64 wavelengths) to waves round robin
@@ -382,16 +419,20 @@ __global__ void __launch_bounds__(kBlock) k_sigma_tw(const SigTabs4 tabv, const 
 
 // per set (prom_transit_set, after new windows): a window's guessed slices (kind 1) are exact (kind |= 4) when every
 // guess is numpy's bracket at every target the window's rows look up (k_seg_exact's test on the windows): k_sigma_tw
-// then reads x_g and the record only, with no bracket test
+// then reads x_g and the record only, with no bracket test.  The window's stage record takes kTwExact with them when
+// every species' slice is a guessed one (tw_stage_of's rule on the marked slices)
 template <int NSIG>
 __global__ void __launch_bounds__(kBlock) k_tw_exact(const SigTabs4 tabv, const double* __restrict__ wav,
                                                      int32_t n_rows, SigSeg* __restrict__ wseg,
-                                                     const int32_t* __restrict__ wrow) {
+                                                     const int32_t* __restrict__ wrow, TwStage* __restrict__ wstg) {
   const int32_t b = blockIdx.x;
   const int32_t* wa = wrow + (int64_t)b * n_rows;
   const int32_t* wz = wa + n_rows;
   __shared__ int32_t bad;
   if (threadIdx.x == 0) bad = 0;
+  bool all1 = true;   // every species' slice a guessed one: the window is exact when they all are
+#pragma unroll
+  for (int s = 0; s < NSIG; ++s) all1 = all1 && (wseg[(int64_t)b * NSIG + s].kind & 3) == 1;
   __syncthreads();
   bool ok = true;
   for (int32_t o = 0; o < n_rows; ++o) {
@@ -419,15 +460,17 @@ __global__ void __launch_bounds__(kBlock) k_tw_exact(const SigTabs4 tabv, const 
     SigSeg& sg = wseg[(int64_t)b * NSIG + threadIdx.x];
     if ((sg.kind & 3) == 1) sg.kind |= 4;
   }
+  if (threadIdx.x == 0 && !bad && all1) wstg[b].mode |= kTwExact;   // (the stage record's mode follows the marks)
 }
 
 void launch_tw_exact(hipStream_t s, TransitDev& tr, int32_t nsig) {
   if (!tr.tw_ok || tr.n_tw <= 0) return;
   SigSeg* twseg = tr.tw_seg.as<SigSeg>();
   const int32_t* twrow = tr.tw_row.as<int32_t>();
+  TwStage* twstg = tr.tw_stage.as<TwStage>();
 #define PROM_TWE(NS)                                                                                            \
   hipLaunchKernelGGL((k_tw_exact<NS>), dim3((unsigned)tr.n_tw), dim3(kBlock), 0, s, tr.sigtab_v, tr.wav.as<double>(), \
-                     tr.n_orb, twseg, twrow)
+                     tr.n_orb, twseg, twrow, twstg)
   switch (nsig) {
     case 1: PROM_TWE(1); break;
     case 2: PROM_TWE(2); break;
@@ -443,7 +486,7 @@ void launch_sigma_tw(hipStream_t s, TransitDev& tr, int32_t nsig, int32_t deg, c
   const unsigned nbw = (unsigned)(((int64_t)tr.n_tw + 7) / 8 * 8);   // one workgroup per window, XCD-interleaved ids
   const SigSeg* twseg = tr.tw_seg.as<SigSeg>();
   const int32_t* twrow = tr.tw_row.as<int32_t>();
-  const int32_t* twlam = tr.tw_lam.as<int32_t>();
+  const TwStage* twstg = tr.tw_stage.as<TwStage>();
   const PolyCoef& pc = poly_coef();
   const SigTabs4& tabv = tr.sigtab_v;
   const SigTabDev* tabp = tr.sigtab.as<SigTabDev>();   // (the same descriptors in device memory: the second pass)
@@ -459,10 +502,10 @@ void launch_sigma_tw(hipStream_t s, TransitDev& tr, int32_t nsig, int32_t deg, c
 #define PROM_TWK(NS, DG, MGV)                                                                                        \
   if (rp == 2)                                                                                                       \
     hipExtLaunchKernelGGL((k_sigma_tw<NS, DG, MGV, 2>), dim3(nbw), dim3(kBlock), 0, s, ev0, ev1, 0, tabv, tabp, pc, wav, \
-                          n_wav, n_rows, twseg, twrow, twlam, tr.n_tw, ta, ta.hdr, tabv.t[0].shift, ta.tab, ta.R);   \
+                          n_wav, n_rows, twseg, twrow, twstg, tr.n_tw, ta, ta.hdr, tabv.t[0].shift, ta.tab, ta.R);   \
   else                                                                                                               \
     hipExtLaunchKernelGGL((k_sigma_tw<NS, DG, MGV, 1>), dim3(nbw), dim3(kBlock), 0, s, ev0, ev1, 0, tabv, tabp, pc, wav, \
-                          n_wav, n_rows, twseg, twrow, twlam, tr.n_tw, ta, ta.hdr, tabv.t[0].shift, ta.tab, ta.R)
+                          n_wav, n_rows, twseg, twrow, twstg, tr.n_tw, ta, ta.hdr, tabv.t[0].shift, ta.tab, ta.R)
 #define PROM_TWD(NS, MGV)                 \
   if (deg <= 8) { PROM_TWK(NS, 8, MGV); } \
   else { PROM_TWK(NS, 14, MGV); }
