@@ -1334,10 +1334,12 @@ int32_t prom_transit_set(prom_ctx* ctx, const prom_transit_problem* pb) {
         if (const char* e = std::getenv("PROM_TC_PARTS"))
           if (std::atoi(e) > 0) tr.tc_parts = std::min(prom::kTcPartMax, std::atoi(e));
         {
-          // the chords' F_out total (the disk sum's denominator, the same for every phase), in chord order
-          double fsum = 0.0;
-          for (int32_t i = 0; i < tr.n_pr; ++i) fsum += pb->chord_fout[i];
-          tr.tc_fsum = fsum;
+          // the chords' F_out total (the disk sum's denominator, the same for every phase), accumulated in long double
+          // and rounded once: a float64 sum in chord order was 12 u off at 16,416 chords, which every R of the phase
+          // carried (tests/test_gpu_tc_sweep.py, the tail at n_pr = 16,416)
+          long double fsum = 0.0L;
+          for (int32_t i = 0; i < tr.n_pr; ++i) fsum += (long double)pb->chord_fout[i];
+          tr.tc_fsum = (double)fsum;
         }
         if (!tr.tc_const.p) {
           // c_k = sum_j f_j cm[k][j] at the nodes u_j = cos(pi (j + 1/2) / 16); node factors 2^((u_k + 1) / 2)

@@ -53,7 +53,10 @@ __device__ __forceinline__ double tc_clenshaw(double q, const double* __restrict
 // octave cap (F_out / F_sum weights).  Not inlined and not optimised: inlined, machine LICM hoists ocml exp's constants
 // out of the lookup kernels' loops and their register allocation grows by ~10-20 VGPRs for paths that run only in
 // pathological cases (k_sigma_tw; k_sigma_tc keeps them inline: there the call's saved registers cost more); the
-// operations and their order are the inlined code's (tc_eval, k_sigma_tc), so the sums are bitwise the same
+// operations and their order are the inlined code's (tc_eval, k_sigma_tc), so the sums are bitwise the same.  Each term
+// is added with an explicit fma in all three places: left as a * b + c, the unoptimised function fused it and the
+// optimised kernels did not (-ffp-contract=off), and the two lookup kernels differed in the last bits beyond a
+// truncated table (tests/test_gpu_tc_sweep.py::test_column_kinds_doppler[two-*])
 #ifndef PROM_TC_CS_ATTR   // (inlined instead, -DPROM_TC_CS_ATTR=__forceinline__: no scratch, 77 VGPRs, no faster: r06z)
 #define PROM_TC_CS_ATTR __noinline__ __attribute__((optnone))
 #endif
@@ -69,7 +72,7 @@ __device__ PROM_TC_CS_ATTR double tc_chord_sum(double Y, bool nf, bool zr, doubl
     double tau = N * Y;
     if (nf && zr && !__builtin_isfinite(N)) tau = __builtin_nan("");
     const double e = exp(-tau);
-    a = nf ? a + fout[ci] * e : a + (fout[ci] * inv_fs) * e;
+    a = nf ? fma(fout[ci], e, a) : fma(fout[ci] * inv_fs, e, a);   // (ocml's: the builtin is a libcall when unoptimised)
   }
   return a;
 }
@@ -97,7 +100,7 @@ __device__ __forceinline__ double tc_eval(double Y, const double* __restrict__ h
   double a = 0.0;
 #pragma unroll 1
   for (int32_t c = 0; c < n_pr; ++c)
-    if (fl[c] == 0) a += (fout[c] * inv_fs) * exp(-(nc[c] * Y));
+    if (fl[c] == 0) a = __builtin_fma(fout[c] * inv_fs, exp(-(nc[c] * Y)), a);
   if (evals) atomicAdd(&evals[threadIdx.x & 63], (unsigned long long)nact);
   return tf + a;
 }

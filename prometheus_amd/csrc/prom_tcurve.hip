@@ -31,8 +31,9 @@
 // atomic loads (global_load ... sc1).  This is MI355X_MICROARCH.md's measured sc1 form, used in place of an
 // agent-scope release/acquire pair (whose release is a buffer_wbl2 of the whole XCD L2: 1.7-6.5 us per workgroup and
 // run).  It relies on the relaxed agent-scope atomics compiling to sc1 accesses; a compiler that lowered them
-// otherwise would need the fences back.  tests/test_gpu_tcurve.py (curves against the exact sums, many parts) would
-// show a stale partial sum as a wrong curve.
+// otherwise would need the fences back.  tests/test_gpu_tcurve.py (curves against the exact sums, 1 and 8 parts) and
+// tests/test_gpu_tc_sweep.py (against the closed-form sum: 1 to 16 parts, both front ends, parts staged in LDS, read
+// from global memory and mixed) would show a stale partial sum as a wrong curve.
 #include "prom_tc.h"
 
 namespace prom {
@@ -388,7 +389,9 @@ __global__ void __launch_bounds__(kTcB2) k_tc_build(const int32_t* __restrict__ 
     t[5] = -t[5] / 120.0;
     double* h = hdr + (int64_t)o * kTcHdr;
     h[kTcHNmax] = nmax;
-    h[kTcHTfrac] = (tcp ? sf[kTcChain][6] : ts) / fs;
+    // (every chord transparent: exactly 1, as the reference's Fin / Fout -- with the partials the transparent sum
+    // and the set's total are added in different orders and their quotient may miss 1 by an ulp)
+    h[kTcHTfrac] = ntr == n_pr ? 1.0 : (tcp ? sf[kTcChain][6] : ts) / fs;
     h[kTcHFsum] = fs;
 #pragma unroll
     for (int e = 0; e < 6; ++e) h[kTcHT0 + e] = t[e];
@@ -698,7 +701,7 @@ __global__ void __launch_bounds__(kBlock) PROM_TC_ATTR k_sigma_tc(const SigTabs4
         const double N = nc[c];
         double tau = N * Y;
         if (zr && !__builtin_isfinite(N)) tau = __builtin_nan("");
-        a = a + ta.fout[c] * exp(-tau);
+        a = __builtin_fma(ta.fout[c], exp(-tau), a);   // (tc_chord_sum's operation)
       }
       const double fs = h[kTcHFsum];
       v = (a + h[kTcHTfrac] * fs) / fs;
