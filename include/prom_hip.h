@@ -265,6 +265,50 @@ int32_t prom_transit_columns(prom_ctx* ctx, double* N_out);
 int32_t prom_transit_band_stats(prom_ctx* ctx, int32_t n_bands, const double* bounds, double* sum_out,
                                 int64_t* count_out, double* max_out);
 
+/* ---- observation of a spectrum on the device -------------------------------------------------
+ * What a retrieval does with R before it compares it with data, over R as it lies in device memory: the
+ * convolution with the spectrograph's Gaussian line-spread function, the sampling on the detector's pixels (per
+ * phase in a frame scaled by f[o], e.g. the planet's rest frame) and the chi-square.  All float64; the roundings
+ * named here are part of the definition.
+ *
+ *   trapezoid weights    q_w = (hi_w - lo_w) / 2, lo_w = wav[w-1] (w = 0: edge_lo, or wav[0] when edge_lo is NaN),
+ *                        hi_w likewise at the top: the weights of the WHOLE grid when a shard or chunk passes the
+ *                        grid points just outside it as edges (NaN: there is none)
+ *   pixel in the model frame   L = fl(lam[p] f[o]), S = fl(sig[p] f[o]), c = fl(k S)   (f NULL: all 1)
+ *   support              the w with |wav[w] - L| <= c (difference in float64, both ends inclusive)
+ *   weight               g_w = exp(-0.5 z z), z = (wav[w] - L) / S
+ *   partial sums         num[o][p] = sum g_w q_w R[o][w], den[o][p] = sum g_w q_w over the support, in an order
+ *                        fixed by the kernel (no floating-point atomics: two calls agree bit for bit).  An empty
+ *                        support gives 0 and 0; a NaN in R reaches exactly the pixels whose support holds it
+ *   model spectrum       M = (sum over shards of num) / (sum over shards of den); den == 0: NaN, no coverage
+ *   chi-square           pixel (o, p) is used when ivar is finite and > 0, data is finite and den > 0;
+ *                        chi2[o] = sum over used pixels of ivar (M - data)^2 in a fixed order, n_used[o] their
+ *                        number.  Formed on the device only when the call sees the whole grid (both edges NaN);
+ *                        with an edge given a request for it is PROM_E_ARG and the caller forms it from the
+ *                        combined partials.
+ * The pixel's own width is not modelled: the caller folds it into sig. */
+
+/* Make the observation resident on the context: pixel centres lam[n_pix] (non-decreasing) and Gaussian widths
+ * sig[n_pix] > 0 in cm, the truncation k > 0 in units of sigma, n_orb phases, and optionally the frame factors
+ * f[n_orb] > 0 (NULL: all 1) and data[n_orb][n_pix] with ivar[n_orb][n_pix] (NULL: no chi-square).  A retrieval
+ * uploads it once.  A later prom_transit_set with another n_orb drops it (the observe calls then fail with
+ * PROM_E_STATE). */
+int32_t prom_observe_set(prom_ctx* ctx, int32_t n_pix, const double* lam, const double* sig, double k, int32_t n_orb,
+                         const double* f, const double* data, const double* ivar);
+/* Observe the last run's R on its stream (as prom_transit_band_stats does).  Every output may be NULL; only the
+ * requested ones are copied back: num_out, den_out [n_orb][n_pix], chi2_out [n_orb], n_used_out [n_orb].  With
+ * n_pix == 0 the call returns PROM_OK and touches nothing. */
+int32_t prom_transit_observe(prom_ctx* ctx, double edge_lo, double edge_hi, double* num_out, double* den_out,
+                             double* chi2_out, int64_t* n_used_out);
+/* The same for a spectrum the caller supplies: wav[n_wav] ascending, R[n_orb][n_wav], n_orb the observation's. */
+int32_t prom_spectrum_observe(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                              double edge_lo, double edge_hi, double* num_out, double* den_out, double* chi2_out,
+                              int64_t* n_used_out);
+/* Measurement aid (tools/observe_bench.py), not for callers: mean device duration in milliseconds of k_observe over
+ * n_runs repetitions of the last observe call's launch (events around its dispatch).  PROM_E_STATE when there is
+ * no such call since the last prom_observe_set or prom_transit_set. */
+int32_t prom_observe_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
+
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop
  * events on its own dispatch packet (groups of kernels: the first start to the last stop).  ms_out[k] is

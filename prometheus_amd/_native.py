@@ -119,6 +119,11 @@ SIGNATURES = {
     "prom_transit_columns": (C.c_int32, [C.c_void_p, _dp]),
     "prom_transit_band_stats": (C.c_int32, [C.c_void_p, C.c_int32, _dp, _dp, C.POINTER(C.c_int64), _dp]),
     "prom_transit_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
+    "prom_observe_set": (C.c_int32, [C.c_void_p, C.c_int32, _dp, _dp, C.c_double, C.c_int32, _dp, _dp, _dp]),
+    "prom_transit_observe": (C.c_int32, [C.c_void_p, C.c_double, C.c_double, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "prom_spectrum_observe": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_double, C.c_double, _dp,
+                                          _dp, _dp, C.POINTER(C.c_int64)]),
+    "prom_observe_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -235,6 +240,9 @@ class Device:
         # tables whose host objects were collected: freed at the next table or problem upload (a
         # finalizer may run while another thread is inside a call on this context)
         self._pending_free: list = []
+        # the observation resident on the context: (n_orb, n_pix) and the caller's key (None: none)
+        self._obs_shape = None
+        self._obs_key = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -360,6 +368,8 @@ class Device:
         self._keep = prob.keepalive
         self._check(self.lib.prom_transit_set(self.h, C.byref(prob.struct)), "prom_transit_set")
         self._shape = (prob.struct.n_orb, prob.struct.n_wav)
+        if self._obs_shape is not None and self._obs_shape[0] != prob.struct.n_orb:
+            self._obs_shape = self._obs_key = None   # the library dropped the observation
         self._n_atoms = prob.n_atoms
         self._n_pr = prob.struct.n_pr
 
@@ -417,6 +427,77 @@ class Device:
                     "prom_transit_band_stats")
         return s, c, m
 
+    # ---- observation (prom_hip.h "observation of a spectrum on the device") -------------------
+    def observe_set(self, lam, sig, k: float, n_orb: int, f=None, data=None, ivar=None, key=None) -> None:
+        """prom_observe_set: pixel centres (non-decreasing) and widths [n_pix], truncation k, the phases' frame
+        factors f [n_orb] (None: all 1) and data / ivar [n_orb][n_pix] (None: no chi-square).  ``key``: any value
+        the caller keeps in ``observe_key`` to skip a later upload of the same observation."""
+        lam, sig = _f64(lam), _f64(sig)
+        if lam.ndim != 1 or sig.shape != lam.shape:
+            raise ValueError("observe_set: lam and sig must be 1-D arrays of one length")
+        n_pix, n_orb = len(lam), int(n_orb)
+        f = None if f is None else _f64(f)
+        if f is not None and f.shape != (n_orb,):
+            raise ValueError("observe_set: f must be [n_orb]")
+        if (data is None) != (ivar is None):
+            raise ValueError("observe_set: data and ivar come together")
+        if data is not None:
+            data, ivar = _f64(data), _f64(ivar)
+            if data.shape != (n_orb, n_pix) or ivar.shape != (n_orb, n_pix):
+                raise ValueError("observe_set: data and ivar must be [n_orb][n_pix]")
+        self._obs_shape = self._obs_key = None
+        self._check(self.lib.prom_observe_set(self.h, n_pix, _d(lam), _d(sig), float(k), n_orb,
+                                              _d(f) if f is not None else None,
+                                              _d(data) if data is not None else None,
+                                              _d(ivar) if ivar is not None else None), "prom_observe_set")
+        self._obs_shape = (n_orb, n_pix)
+        self._obs_key = key
+
+    @property
+    def observe_key(self):
+        """The ``key`` of the observation resident on the context (None: none, or set without a key)."""
+        return self._obs_key
+
+    def _observe_outputs(self, partials: bool, chi2: bool):
+        shape = self._obs_shape or (0, 0)
+        num = den = None
+        if partials:
+            # large partial sums land in page-locked memory from the library's pool (one DMA each at the link rate)
+            big = shape[0] * shape[1] * 8 >= (1 << 20)
+            num = host_array(shape) if big else None
+            den = host_array(shape) if big else None
+            num = np.zeros(shape) if num is None else num
+            den = np.zeros(shape) if den is None else den
+        c2 = np.zeros(shape[0]) if chi2 else None
+        nu = np.zeros(shape[0], dtype=np.int64) if chi2 else None
+        ptr = (_d(num) if partials else None, _d(den) if partials else None, _d(c2) if chi2 else None,
+               nu.ctypes.data_as(C.POINTER(C.c_int64)) if chi2 else None)
+        return (num, den, c2, nu), ptr
+
+    def transit_observe(self, edge_lo: float = np.nan, edge_hi: float = np.nan, partials: bool = True,
+                        chi2: bool = False):
+        """prom_transit_observe over the last run's R: (num, den, chi2, n_used), None for what was not asked."""
+        out, ptr = self._observe_outputs(partials, chi2)
+        self._check(self.lib.prom_transit_observe(self.h, float(edge_lo), float(edge_hi), *ptr),
+                    "prom_transit_observe")
+        return out
+
+    def spectrum_observe(self, wav, R, edge_lo: float = np.nan, edge_hi: float = np.nan, partials: bool = True,
+                         chi2: bool = False):
+        """prom_spectrum_observe of R[n_orb][n_wav] on the ascending grid wav: (num, den, chi2, n_used)."""
+        wav, R = _f64(wav), _f64(R)
+        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
+            raise ValueError("spectrum_observe: R must be [n_orb][n_wav]")
+        out, ptr = self._observe_outputs(partials, chi2)
+        self._check(self.lib.prom_spectrum_observe(self.h, R.shape[0], len(wav), _d(wav), _d(R), float(edge_lo),
+                                                   float(edge_hi), *ptr), "prom_spectrum_observe")
+        return out
+
+    def observe_kernel_ms(self, n_runs: int = 20) -> float:
+        """prom_observe_kernel_ms: mean device duration [ms] of k_observe for the last observe call's launch."""
+        ms = C.c_double(0.0)
+        self._check(self.lib.prom_observe_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_observe_kernel_ms")
+        return float(ms.value)
 
     # ---- stellar disk -----------------------------------------------------------------------
     def star_disk_flux(self, table_id: int, shift, clv, rho, dphi: float, drho: float, wavelength) -> np.ndarray:

@@ -592,6 +592,8 @@ int32_t prom_transit_set(prom_ctx* ctx, const prom_transit_problem* pb) {
     tr.n_wav = pb->n_wav;
     tr.n_pr = pb->n_pr;
     tr.n_orb = pb->n_orb;
+    if (ctx->obs.set && ctx->obs.n_orb != pb->n_orb) ctx->obs.set = false;   // the observation's phases are gone
+    ctx->obs.last_wav = ctx->obs.last_R = nullptr;   // (this set may move the buffers the last observe call read)
     tr.n_x = pb->n_x;
     tr.n_sc = pb->n_scenarios;
     tr.n_moons = pb->n_moons;
@@ -1790,6 +1792,147 @@ int32_t prom_timing_end(prom_ctx* ctx, int32_t max_runs, double* ms, int32_t* n_
     }
     *n_runs = ctx->timed_runs;
     ctx->timed_runs = 0;
+  });
+}
+
+// ------------------------------------------------------------------------------ observation
+static bool obs_finite(double v) { return std::isfinite(v); }
+
+int32_t prom_observe_set(prom_ctx* ctx, int32_t n_pix, const double* lam, const double* sig, double k, int32_t n_orb,
+                         const double* f, const double* data, const double* ivar) {
+  return guarded(ctx, [&] {
+    prom::ObsDev& ob = ctx->obs;
+    ob.set = false;
+    PROM_REQUIRE(n_pix >= 0 && n_orb >= 1 && n_orb <= 65535 && (n_pix == 0 || (lam && sig)),
+                 "prom_observe_set: bad shape");
+    PROM_REQUIRE(k > 0.0 && obs_finite(k), "prom_observe_set: the truncation k must be positive");
+    PROM_REQUIRE((data == nullptr) == (ivar == nullptr), "prom_observe_set: data and ivar come together");
+    for (int32_t p = 0; p < n_pix; ++p) {
+      PROM_REQUIRE(obs_finite(lam[p]) && (p == 0 || lam[p] >= lam[p - 1]),
+                   "prom_observe_set: pixel centres must be finite and non-decreasing");
+      PROM_REQUIRE(sig[p] > 0.0 && obs_finite(sig[p]), "prom_observe_set: widths must be positive");
+    }
+    bool ones = true;
+    for (int32_t o = 0; f && o < n_orb; ++o) {
+      PROM_REQUIRE(f[o] > 0.0 && obs_finite(f[o]), "prom_observe_set: frame factors must be positive");
+      ones = ones && f[o] == 1.0;
+    }
+    const hipStream_t st = ctx->stream;
+    const int64_t n = (int64_t)n_orb * n_pix;
+    upload(ob.lam, lam, n_pix, st);
+    upload(ob.sig, sig, n_pix, st);
+    ob.has_f = f && !ones;   // all ones: the shared-frame path, the same sums bit for bit
+    if (ob.has_f) upload(ob.f, f, n_orb, st);
+    ob.has_data = data != nullptr;
+    if (ob.has_data) {
+      upload(ob.data, data, n, st);
+      upload(ob.ivar, ivar, n, st);
+    }
+    ob.num.ensure(sizeof(double) * (size_t)std::max<int64_t>(n, 1));
+    ob.den.ensure(sizeof(double) * (size_t)std::max<int64_t>(n, 1));
+    ob.chi2.ensure(sizeof(double) * n_orb);
+    ob.n_used.ensure(sizeof(int64_t) * n_orb);
+    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
+    ob.n_pix = n_pix;
+    ob.n_orb = n_orb;
+    ob.k = k;
+    ob.last_wav = ob.last_R = nullptr;
+    ob.set = true;
+  });
+}
+
+// the shared tail of the two observe calls: q, the sums, chi-square and the copies back, on stream st
+static void observe_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav,
+                       double edge_lo, double edge_hi, double* num_out, double* den_out, double* chi2_out,
+                       int64_t* n_used_out) {
+  prom::ObsDev& ob = ctx->obs;
+  const bool want_chi2 = chi2_out || n_used_out;
+  const int64_t n = (int64_t)ob.n_orb * ob.n_pix;
+  ob.q.ensure(sizeof(double) * (size_t)n_wav);
+  prom::launch_observe_q(st, wav, (int32_t)n_wav, edge_lo, edge_hi, ob.q.as<double>());
+  prom::launch_observe(st, wav, ob.q.as<double>(), R, (int32_t)n_wav, ob.lam.as<double>(), ob.sig.as<double>(),
+                       ob.has_f ? ob.f.as<double>() : nullptr, ob.k, ob.n_pix, ob.n_orb, ob.num.as<double>(),
+                       ob.den.as<double>(), nullptr, nullptr);
+  ob.last_wav = wav;
+  ob.last_R = R;
+  ob.last_n_wav = (int32_t)n_wav;
+  if (want_chi2)
+    prom::launch_observe_chi2(st, ob.num.as<double>(), ob.den.as<double>(), ob.data.as<double>(),
+                              ob.ivar.as<double>(), ob.n_pix, ob.n_orb, ob.chi2.as<double>(),
+                              ob.n_used.as<int64_t>());
+  if (num_out) download(num_out, ob.num, n, st);
+  if (den_out) download(den_out, ob.den, n, st);
+  if (chi2_out) download(chi2_out, ob.chi2, ob.n_orb, st);
+  if (n_used_out) download(n_used_out, ob.n_used, ob.n_orb, st);
+  PROM_HIP(hipStreamSynchronize(st));
+}
+
+static void observe_check(const prom::ObsDev& ob, const char* who, double edge_lo, double edge_hi, bool want_chi2) {
+  if (!ob.set)
+    throw Error(PROM_E_STATE, std::string(who) + ": no observation on the context (prom_observe_set; a "
+                                                 "prom_transit_set with another n_orb drops it)");
+  PROM_REQUIRE(!want_chi2 || (edge_lo != edge_lo && edge_hi != edge_hi),
+               std::string(who) + ": chi-square needs the whole grid (both edges NaN)");
+  PROM_REQUIRE(!want_chi2 || ob.has_data, std::string(who) + ": chi-square needs data and ivar (prom_observe_set)");
+  PROM_REQUIRE(!std::isinf(edge_lo) && !std::isinf(edge_hi), std::string(who) + ": infinite edge");
+}
+
+int32_t prom_transit_observe(prom_ctx* ctx, double edge_lo, double edge_hi, double* num_out, double* den_out,
+                             double* chi2_out, int64_t* n_used_out) {
+  return guarded(ctx, [&] {
+    prom::TransitDev& tr = ctx->tr;
+    prom::ObsDev& ob = ctx->obs;
+    observe_check(ob, "prom_transit_observe", edge_lo, edge_hi, chi2_out || n_used_out);
+    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_observe: no completed run");
+    if (ob.n_orb != tr.n_orb) throw Error(PROM_E_STATE, "prom_transit_observe: the observation has another n_orb");
+    if (ob.n_pix == 0) return;
+    // the last run's stream orders the observation after it
+    observe_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, edge_lo,
+               edge_hi, num_out, den_out, chi2_out, n_used_out);
+  });
+}
+
+int32_t prom_spectrum_observe(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                              double edge_lo, double edge_hi, double* num_out, double* den_out, double* chi2_out,
+                              int64_t* n_used_out) {
+  return guarded(ctx, [&] {
+    prom::ObsDev& ob = ctx->obs;
+    observe_check(ob, "prom_spectrum_observe", edge_lo, edge_hi, chi2_out || n_used_out);
+    PROM_REQUIRE(n_orb == ob.n_orb, "prom_spectrum_observe: n_orb differs from the observation's");
+    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_observe: bad spectrum");
+    for (int64_t w = 0; w < n_wav; ++w)
+      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
+                   "prom_spectrum_observe: wavelengths must be finite and ascending");
+    PROM_REQUIRE((edge_lo != edge_lo || edge_lo <= wav[0]) && (edge_hi != edge_hi || edge_hi >= wav[n_wav - 1]),
+                 "prom_spectrum_observe: the edges lie outside the grid");
+    if (ob.n_pix == 0) return;
+    const hipStream_t st = ctx->stream;
+    upload(ob.wav, wav, n_wav, st);
+    upload(ob.R, R, (int64_t)n_orb * n_wav, st);
+    observe_on(ctx, st, ob.wav.as<double>(), ob.R.as<double>(), n_wav, edge_lo, edge_hi, num_out, den_out, chi2_out,
+               n_used_out);
+  });
+}
+
+int32_t prom_observe_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
+  return guarded(ctx, [&] {
+    prom::ObsDev& ob = ctx->obs;
+    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_observe_kernel_ms: bad arguments");
+    if (!ob.set || !ob.last_wav || ob.n_pix == 0)
+      throw Error(PROM_E_STATE, "prom_observe_kernel_ms: no observe call to repeat");
+    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
+    const hipStream_t st = ctx->stream;
+    double sum = 0.0;
+    for (int32_t r = 0; r < n_runs; ++r) {
+      prom::launch_observe(st, ob.last_wav, ob.q.as<double>(), ob.last_R, ob.last_n_wav, ob.lam.as<double>(),
+                           ob.sig.as<double>(), ob.has_f ? ob.f.as<double>() : nullptr, ob.k, ob.n_pix, ob.n_orb,
+                           ob.num.as<double>(), ob.den.as<double>(), ctx->ev[0], ctx->ev[1]);
+      PROM_HIP(hipStreamSynchronize(st));
+      float ms = 0.0f;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      sum += ms;
+    }
+    *ms_out = sum / n_runs;
   });
 }
 

@@ -418,6 +418,21 @@ struct TransitDev {
   int last = 0;                             // slot of the most recent run
 };
 
+// The observation resident on a context (prom_observe_set) and the work buffers of the observe calls.
+struct ObsDev {
+  bool set = false;
+  int32_t n_pix = 0, n_orb = 0;
+  double k = 0.0;
+  bool has_f = false, has_data = false;   // (f given and not all ones; data and ivar given)
+  DevBuf lam, sig, f, data, ivar;         // [n_pix], [n_pix], [n_orb], [n_orb][n_pix] x 2
+  DevBuf q, num, den, chi2, n_used;       // [n_wav], [n_orb][n_pix] x 2, [n_orb], [n_orb] int64
+  DevBuf wav, R;                          // prom_spectrum_observe's copies of the caller's spectrum
+  // the last k_observe launch, for prom_observe_kernel_ms to repeat (null: none yet)
+  const double* last_wav = nullptr;
+  const double* last_R = nullptr;
+  int32_t last_n_wav = 0;
+};
+
 }  // namespace prom
 
 struct prom_ctx {
@@ -430,6 +445,7 @@ struct prom_ctx {
   std::vector<prom::AtomTable> tables;
   std::vector<prom::MolTable> mtables;
   prom::TransitDev tr;
+  prom::ObsDev obs;
   prom::DevBuf scratch[6];
   bool timing = false;
   std::vector<hipEvent_t> tev;   // pool, 4 per timed run
@@ -506,6 +522,13 @@ void launch_scatter(hipStream_t s, const char* base, const ScatterDesc* d, int32
 // per phase: sum / count of R over the band-selected wavelengths, max of R over all (prom_transit_band_stats)
 void launch_band_stats(hipStream_t s, const double* R, const double* wav, int32_t n_orb, int64_t n_wav,
                        int32_t n_bands, const double* bounds, double* sum, int64_t* count, double* mx);
+// the observation of a spectrum (prom_observe.hip): trapezoid weights, the LSF sums per (phase, pixel), chi-square
+void launch_observe_q(hipStream_t s, const double* wav, int32_t n_wav, double edge_lo, double edge_hi, double* q);
+void launch_observe(hipStream_t s, const double* wav, const double* q, const double* R, int32_t n_wav,
+                    const double* lam, const double* sig, const double* f, double k, int32_t n_pix, int32_t n_orb,
+                    double* num, double* den, hipEvent_t ev0, hipEvent_t ev1);
+void launch_observe_chi2(hipStream_t s, const double* num, const double* den, const double* data, const double* ivar,
+                         int32_t n_pix, int32_t n_orb, double* chi2, int64_t* n_used);
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

@@ -1,0 +1,143 @@
+"""Observing a transit spectrum: the instrument's line-spread function, the detector's pixels, chi-square.
+
+The model grid is far finer than any detector (0.001 A in the line cores).  Before R meets data it is convolved
+with the spectrograph's Gaussian line-spread function and sampled on the detector's pixels, often in the planet's
+rest frame (one Doppler factor per phase), and a chi-square is formed.  Here that runs on the device over R as it
+stays in HBM after the run (prom_transit_observe; the definition is in include/prom_hip.h): a likelihood evaluation
+brings back a few numbers per phase, or a pixel spectrum far smaller than R.  The host forms the O(n_pix) pixel
+tables and combines the partial sums of wavelength shards and chunks.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+FWHM_PER_SIGMA = 2.0 * math.sqrt(2.0 * math.log(2.0))
+
+
+class Instrument:
+    """Detector pixels and the Gaussian line-spread function at each of them.
+
+    ``pixels``: pixel centres in cm, in any order (echelle orders overlap): they are sorted for the device and
+    results come back in the caller's order.  The width is ``sigma`` (cm, scalar or per pixel) or follows from
+    ``resolving_power`` (scalar or per pixel) as sigma = pixel / (resolving_power 2 sqrt(2 ln 2)).  The pixel's own
+    width is not modelled: fold it into sigma.  ``truncate``: the support of the kernel in units of sigma."""
+
+    def __init__(self, pixels, resolving_power=None, sigma=None, truncate: float = 5.0):
+        px = np.array(pixels, dtype=np.float64).reshape(-1)
+        if (resolving_power is None) == (sigma is None):
+            raise ValueError("Instrument: give resolving_power or sigma")
+        if sigma is None:
+            sg = px / (np.asarray(resolving_power, dtype=np.float64) * FWHM_PER_SIGMA)
+        else:
+            sg = np.asarray(sigma, dtype=np.float64)
+        sg = np.array(np.broadcast_to(sg, px.shape), dtype=np.float64)
+        if not (np.all(np.isfinite(px)) and np.all(np.isfinite(sg)) and np.all(sg > 0)):
+            raise ValueError("Instrument: pixels must be finite and sigma positive")
+        if not (truncate > 0 and math.isfinite(truncate)):
+            raise ValueError("Instrument: truncate must be positive")
+        self.pixels, self.sigma, self.truncate = px, sg, float(truncate)
+        self.order = np.argsort(px, kind="stable")
+        self.lam = np.ascontiguousarray(px[self.order])   # what the device sees
+        self.sig = np.ascontiguousarray(sg[self.order])
+
+    @property
+    def n_pix(self) -> int:
+        return len(self.pixels)
+
+    def sort(self, a):
+        """[..., n_pix] in the caller's pixel order -> the device's (ascending) order."""
+        return np.ascontiguousarray(np.asarray(a, dtype=np.float64)[..., self.order])
+
+    def unsort(self, a):
+        """[..., n_pix] in the device's order -> the caller's."""
+        a = np.asarray(a)
+        out = np.empty_like(a)
+        out[..., self.order] = a
+        return out
+
+    def full_weight(self, frame=None):
+        """The integral of the truncated kernel, sigma sqrt(2 pi) erf(k / sqrt 2) per pixel ([n_pix], or
+        [n_orb][n_pix] with the phases' frame factors): den of a pixel whose support the grid covers densely."""
+        s = self.sigma if frame is None else np.asarray(frame, dtype=np.float64)[:, None] * self.sigma[None, :]
+        return s * (math.sqrt(2.0 * math.pi) * math.erf(self.truncate / math.sqrt(2.0)))
+
+
+class Observation:
+    """What stays resident on the device between likelihood evaluations: the instrument's pixels, the phases' frame
+    factors ``frame_shifts`` [n_orb] (None: the model's own frame) and ``data`` with its standard error ``err``
+    ([n_orb][n_pix] in the caller's pixel order, or anything that broadcasts to it; a pixel with non-finite data or
+    err, or err <= 0, is masked).  Sorting, the inverse variances and the content key that lets a device skip the
+    upload are computed once here: a retrieval loop builds one Observation and hands it to every Transit.observe
+    call, which then neither hashes nor uploads the data again.  The arrays are copied: later changes to the
+    caller's arrays need a new Observation."""
+
+    def __init__(self, instrument: Instrument, n_orb: int, frame_shifts=None, data=None, err=None):
+        from .gasProperties import _content_fingerprint
+        self.instrument, self.n_orb = instrument, int(n_orb)
+        self.f = None
+        if frame_shifts is not None:
+            self.f = np.array(frame_shifts, dtype=np.float64)
+            if self.f.shape != (self.n_orb,):
+                raise ValueError("Observation: frame_shifts must have one factor per orbital phase")
+        if (data is None) != (err is None):
+            raise ValueError("Observation: data and err come together")
+        self.data = self.ivar = None
+        if data is not None:
+            shape = (self.n_orb, instrument.n_pix)
+            self.data = instrument.sort(np.broadcast_to(np.asarray(data, dtype=np.float64), shape))
+            e = instrument.sort(np.broadcast_to(np.asarray(err, dtype=np.float64), shape))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                self.ivar = np.where(np.isfinite(e) & (e > 0), 1.0 / (e * e), 0.0)
+        arrays = [instrument.lam, instrument.sig] + [a for a in (self.f, self.data, self.ivar) if a is not None]
+        self.key = (self.n_orb, instrument.truncate, self.f is None, self.data is None) + _content_fingerprint(*arrays)
+
+
+def model_spectrum(num, den) -> np.ndarray:
+    """M = num / den; NaN where den == 0 (no model coverage)."""
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(den == 0.0, np.nan, num / np.where(den == 0.0, 1.0, den))
+
+
+def chi_square(model, den, data, ivar):
+    """(chi2[n_orb], n_used[n_orb]) on the host, with the device's rule: a pixel is used when ivar is finite and
+    > 0, data is finite and den > 0; a used pixel with NaN model makes the phase's chi2 NaN."""
+    model, den, data, ivar = (np.asarray(a, dtype=np.float64) for a in (model, den, data, ivar))
+    with np.errstate(invalid="ignore"):
+        used = np.isfinite(ivar) & (ivar > 0) & np.isfinite(data) & (den > 0)
+        r = np.where(used, model - data, 0.0)
+        terms = np.where(used, np.where(used, ivar, 0.0) * (r * r), 0.0)
+    return terms.sum(axis=-1), used.sum(axis=-1).astype(np.int64)
+
+
+def coadd(model, weights=None) -> np.ndarray:
+    """Weighted mean over phases of model[n_orb][n_pix], over the phases whose model is finite at the pixel: the
+    planet-frame co-addition that ``frame_shifts`` exists for.  ``weights``: [n_orb] or [n_orb][n_pix] (default
+    1).  NaN where no phase has a finite model or the weights sum to 0."""
+    m = np.asarray(model, dtype=np.float64)
+    w = np.ones(m.shape[0]) if weights is None else np.asarray(weights, dtype=np.float64)
+    w = np.broadcast_to(w[:, None] if w.ndim == 1 else w, m.shape)
+    ok = np.isfinite(m) & np.isfinite(w)
+    ws = np.where(ok, w, 0.0)
+    tot = ws.sum(axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(tot != 0.0, (ws * np.where(ok, m, 0.0)).sum(axis=0) / np.where(tot != 0.0, tot, 1.0), np.nan)
+
+
+def planet_frame_shifts(planet, orbphase) -> np.ndarray:
+    """Per-phase frame factors of the planet's rest frame (lightcurve.planet_shifts): a pixel at rest wavelength
+    lambda sits at lambda * factor in the model's frame."""
+    from . import lightcurve
+    return lightcurve.planet_shifts(planet, orbphase)
+
+
+class Observed:
+    """Result of Transit.observe, in the caller's pixel order: ``model`` [n_orb][n_pix] (None when not asked),
+    ``coverage`` = den / (sigma sqrt(2 pi) erf(k / sqrt 2)) (1 where the grid covers a pixel's support densely, less
+    at the grid's ends, 0 outside), ``chi2`` and ``n_used`` [n_orb] (None without data), ``spectrum`` R (None
+    unless asked)."""
+
+    def __init__(self, model=None, coverage=None, chi2=None, n_used=None, spectrum=None):
+        self.model, self.coverage, self.chi2, self.n_used, self.spectrum = model, coverage, chi2, n_used, spectrum
