@@ -309,6 +309,55 @@ int32_t prom_spectrum_observe(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const
  * no such call since the last prom_observe_set or prom_transit_set. */
 int32_t prom_observe_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
 
+/* ---- velocity maps on the device -------------------------------------------------------------
+ * The observation's model spectrum in many trial frames at once, compared with the data: for every phase o and
+ * trial j of a resident table F[n_orb][n_trial] of frame factors (a grid of trial velocities, or a (Kp, Vsys)
+ * grid), the seven inverse-variance weighted moments of model against data.  Chi-square, chi-square with a free
+ * scale, the weighted cross-correlation and a Brogi & Line log-likelihood follow from them on the host
+ * (prometheus_amd/observation.py, VelocityMap).  All float64; the roundings named here are part of the definition.
+ *
+ *   inputs               the resident observation (prom_observe_set) with data and ivar; the table F, every entry
+ *                        finite and > 0; a spectrum wav[n_wav], R[n_orb][n_wav] that covers the whole grid (both
+ *                        edges NaN in the trapezoid weights: there are no shard partials)
+ *   frame of trial (o, j)  F[o][j] alone is the factor; the observation's own f[o] is not applied.  Pixel p has
+ *                        L = fl(lam[p] F[o][j]), S = fl(sig[p] F[o][j]), c = fl(k S); the support, the weights g and
+ *                        q, num, den and M = num / den are those of the observation's definition above with f[o]
+ *                        replaced by F[o][j] (num and den added over the support in an order fixed by the kernel)
+ *   used pixels          ivar[o][p] finite and > 0, data[o][p] finite, den > 0 (the chi-square's rule)
+ *   moments              over the used pixels, with iv = ivar and d = data:
+ *                          m0 = sum iv          m1 = sum fl(iv M)         m2 = sum fl(iv d)
+ *                          m3 = sum fl(fl(iv M) M)   m4 = sum fl(fl(iv M) d)   m5 = sum fl(fl(iv d) d)
+ *                          m6 = sum fl(iv fl((M - d)^2)), formed directly and not from the others
+ *                        and n_used (int64), their number
+ *   order, edge cases    the order of every sum is fixed by the kernels (no floating-point atomics); with no used
+ *                        pixel every moment is 0 and n_used is 0; a used pixel with NaN M makes m1, m3, m4 and m6
+ *                        of that (o, j) NaN and leaves m0, m2, m5 and n_used alone
+ *   independence         the eight numbers of trial (o, j) depend only on the spectrum, the observation and the
+ *                        value F[o][j]: not on n_trial, the column's position in the table, the other columns,
+ *                        whether a support was read from LDS or from global memory, or how the launcher splits the
+ *                        table into batches.  Two calls agree bit for bit. */
+
+/* Make the trial table F[n_orb][n_trial] resident.  n_trial >= 1 and every entry finite and > 0, otherwise
+ * PROM_E_ARG; the context must hold an observation with data and the same n_orb, otherwise PROM_E_STATE.  A later
+ * prom_observe_set, or a prom_transit_set with another n_orb, drops the table (the map calls then fail with
+ * PROM_E_STATE). */
+int32_t prom_vmap_set(prom_ctx* ctx, int32_t n_orb, int32_t n_trial, const double* F);
+/* The map over the last run's R on its stream (as prom_transit_observe): mom_out [n_orb][n_trial][7] and
+ * n_used_out [n_orb][n_trial]; either may be NULL.  The partial records of the kernel take
+ * n_orb * n_trial * ceil(ceil(n_pix / 32) / 16) * 64 bytes of device scratch, capped at 256 MiB, or at
+ * PROM_VMAP_SCRATCH_MB megabytes (fractions allowed) from the environment at context creation: a larger table runs in
+ * batches of whole groups of 8 trials (one group at least), with the same results bit for bit. */
+int32_t prom_transit_vmap(prom_ctx* ctx, double* mom_out, int64_t* n_used_out);
+/* The same for a spectrum the caller supplies: wav[n_wav] finite and ascending, R[n_orb][n_wav], n_orb the table's
+ * (the checks of prom_spectrum_observe). */
+int32_t prom_spectrum_vmap(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                           double* mom_out, int64_t* n_used_out);
+/* Measurement aid (tools/vmap_bench.py), not for callers: mean device duration in milliseconds of k_vmap over n_runs
+ * repetitions of the last map call (events around the first batch's dispatch, scaled by n_trial over the batch's
+ * trials when the table runs in several batches).  PROM_E_STATE when there is no such call since the last
+ * prom_transit_set, prom_observe_set or prom_vmap_set. */
+int32_t prom_vmap_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
+
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop
  * events on its own dispatch packet (groups of kernels: the first start to the last stop).  ms_out[k] is

@@ -124,6 +124,10 @@ SIGNATURES = {
     "prom_spectrum_observe": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_double, C.c_double, _dp,
                                           _dp, _dp, C.POINTER(C.c_int64)]),
     "prom_observe_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
+    "prom_vmap_set": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp]),
+    "prom_transit_vmap": (C.c_int32, [C.c_void_p, _dp, C.POINTER(C.c_int64)]),
+    "prom_spectrum_vmap": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "prom_vmap_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -243,6 +247,8 @@ class Device:
         # the observation resident on the context: (n_orb, n_pix) and the caller's key (None: none)
         self._obs_shape = None
         self._obs_key = None
+        self._vm_shape = None
+        self._vm_key = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -370,6 +376,7 @@ class Device:
         self._shape = (prob.struct.n_orb, prob.struct.n_wav)
         if self._obs_shape is not None and self._obs_shape[0] != prob.struct.n_orb:
             self._obs_shape = self._obs_key = None   # the library dropped the observation
+            self._vm_shape = self._vm_key = None     # ... and the trial table with it
         self._n_atoms = prob.n_atoms
         self._n_pr = prob.struct.n_pr
 
@@ -446,6 +453,7 @@ class Device:
             if data.shape != (n_orb, n_pix) or ivar.shape != (n_orb, n_pix):
                 raise ValueError("observe_set: data and ivar must be [n_orb][n_pix]")
         self._obs_shape = self._obs_key = None
+        self._vm_shape = self._vm_key = None   # the library drops the trial table with the observation it was set for
         self._check(self.lib.prom_observe_set(self.h, n_pix, _d(lam), _d(sig), float(k), n_orb,
                                               _d(f) if f is not None else None,
                                               _d(data) if data is not None else None,
@@ -497,6 +505,53 @@ class Device:
         """prom_observe_kernel_ms: mean device duration [ms] of k_observe for the last observe call's launch."""
         ms = C.c_double(0.0)
         self._check(self.lib.prom_observe_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_observe_kernel_ms")
+        return float(ms.value)
+
+    # ---- velocity maps (prom_hip.h "velocity maps on the device") -----------------------------
+    def vmap_set(self, F, key=None) -> None:
+        """prom_vmap_set: the trial table F[n_orb][n_trial] of frame factors (finite, > 0) for the resident
+        observation, which must hold data.  ``key``: any value the caller keeps in ``vmap_key`` to skip a later upload
+        of the same table."""
+        F = _f64(F)
+        if F.ndim != 2:
+            raise ValueError("vmap_set: F must be [n_orb][n_trial]")
+        self._vm_shape = self._vm_key = None
+        self._check(self.lib.prom_vmap_set(self.h, F.shape[0], F.shape[1], _d(F)), "prom_vmap_set")
+        self._vm_shape = F.shape
+        self._vm_key = key
+
+    @property
+    def vmap_key(self):
+        """The ``key`` of the trial table resident on the context (None: none, or set without a key)."""
+        return self._vm_key
+
+    def _vmap_outputs(self):
+        shape = self._vm_shape or (0, 0)
+        mom = np.zeros(shape + (7,))
+        nu = np.zeros(shape, dtype=np.int64)
+        return mom, nu
+
+    def transit_vmap(self):
+        """prom_transit_vmap over the last run's R: (moments [n_orb][n_trial][7], n_used [n_orb][n_trial])."""
+        mom, nu = self._vmap_outputs()
+        self._check(self.lib.prom_transit_vmap(self.h, _d(mom), nu.ctypes.data_as(C.POINTER(C.c_int64))),
+                    "prom_transit_vmap")
+        return mom, nu
+
+    def spectrum_vmap(self, wav, R):
+        """prom_spectrum_vmap of R[n_orb][n_wav] on the ascending grid wav: (moments, n_used)."""
+        wav, R = _f64(wav), _f64(R)
+        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
+            raise ValueError("spectrum_vmap: R must be [n_orb][n_wav]")
+        mom, nu = self._vmap_outputs()
+        self._check(self.lib.prom_spectrum_vmap(self.h, R.shape[0], len(wav), _d(wav), _d(R), _d(mom),
+                                                nu.ctypes.data_as(C.POINTER(C.c_int64))), "prom_spectrum_vmap")
+        return mom, nu
+
+    def vmap_kernel_ms(self, n_runs: int = 20) -> float:
+        """prom_vmap_kernel_ms: mean device duration [ms] of k_vmap for the last map call's launch."""
+        ms = C.c_double(0.0)
+        self._check(self.lib.prom_vmap_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_vmap_kernel_ms")
         return float(ms.value)
 
     # ---- stellar disk -----------------------------------------------------------------------

@@ -12,6 +12,7 @@
 
 #include "prom_internal.h"
 #include "tw_stage.h"
+#include "vmap_index.h"
 
 using prom::DevBuf;
 using prom::Error;
@@ -245,6 +246,11 @@ int32_t prom_create(int32_t device, prom_ctx** out) {
     ok = hipStreamCreateWithFlags(&ctx->streams[i], hipStreamNonBlocking) == hipSuccess;
   ctx->stream = ctx->streams[0];
   if (const char* e = std::getenv("PROM_PIPELINE")) ctx->pipeline = std::max(1, std::min(prom::kMaxSlots, std::atoi(e)));
+  // (megabytes, fractions allowed; a map that needs more runs in batches of whole trial groups, one group at least)
+  if (const char* e = std::getenv("PROM_VMAP_SCRATCH_MB")) {
+    const double mb = std::atof(e);
+    if (mb > 0.0 && mb < 1.0e6) ctx->vmap_scratch_bytes = std::max<int64_t>(1, (int64_t)(mb * 1048576.0));
+  }
   if (!ok) {
     delete ctx;
     return PROM_E_HIP;
@@ -594,6 +600,8 @@ int32_t prom_transit_set(prom_ctx* ctx, const prom_transit_problem* pb) {
     tr.n_orb = pb->n_orb;
     if (ctx->obs.set && ctx->obs.n_orb != pb->n_orb) ctx->obs.set = false;   // the observation's phases are gone
     ctx->obs.last_wav = ctx->obs.last_R = nullptr;   // (this set may move the buffers the last observe call read)
+    if (ctx->vm.set && ctx->vm.n_orb != pb->n_orb) ctx->vm.set = false;      // ... and the trial table's with them
+    ctx->vm.last_wav = ctx->vm.last_R = nullptr;
     tr.n_x = pb->n_x;
     tr.n_sc = pb->n_scenarios;
     tr.n_moons = pb->n_moons;
@@ -1803,6 +1811,8 @@ int32_t prom_observe_set(prom_ctx* ctx, int32_t n_pix, const double* lam, const 
   return guarded(ctx, [&] {
     prom::ObsDev& ob = ctx->obs;
     ob.set = false;
+    ctx->vm.set = false;   // a trial table belongs to the observation it was set for
+    ctx->vm.last_wav = ctx->vm.last_R = nullptr;
     PROM_REQUIRE(n_pix >= 0 && n_orb >= 1 && n_orb <= 65535 && (n_pix == 0 || (lam && sig)),
                  "prom_observe_set: bad shape");
     PROM_REQUIRE(k > 0.0 && obs_finite(k), "prom_observe_set: the truncation k must be positive");
@@ -1933,6 +1943,139 @@ int32_t prom_observe_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
       sum += ms;
     }
     *ms_out = sum / n_runs;
+  });
+}
+
+// ------------------------------------------------------------------------------ velocity maps
+int32_t prom_vmap_set(prom_ctx* ctx, int32_t n_orb, int32_t n_trial, const double* F) {
+  return guarded(ctx, [&] {
+    prom::VmDev& vm = ctx->vm;
+    const prom::ObsDev& ob = ctx->obs;
+    vm.set = false;
+    vm.last_wav = vm.last_R = nullptr;
+    PROM_REQUIRE(n_orb >= 1 && n_trial >= 1 && n_trial <= (1 << 24) && F, "prom_vmap_set: bad shape");
+    if (!ob.set)
+      throw Error(PROM_E_STATE, "prom_vmap_set: no observation on the context (prom_observe_set)");
+    if (!ob.has_data)
+      throw Error(PROM_E_STATE, "prom_vmap_set: the observation has no data and ivar (prom_observe_set)");
+    if (ob.n_orb != n_orb) throw Error(PROM_E_STATE, "prom_vmap_set: the observation has another n_orb");
+    const int64_t n = (int64_t)n_orb * n_trial;
+    PROM_REQUIRE(n <= ((int64_t)1 << 28), "prom_vmap_set: table too large");
+    for (int64_t i = 0; i < n; ++i)
+      PROM_REQUIRE(F[i] > 0.0 && obs_finite(F[i]), "prom_vmap_set: trial factors must be finite and positive");
+    const hipStream_t st = ctx->stream;
+    upload(vm.F, F, n, st);
+    vm.mom.ensure(sizeof(double) * 7 * (size_t)n);
+    vm.n_used.ensure(sizeof(int64_t) * (size_t)n);
+    PROM_HIP(hipStreamSynchronize(st));   // the host array is read during the call only
+    vm.n_orb = n_orb;
+    vm.n_trial = n_trial;
+    vm.set = true;
+  });
+}
+
+// one pass over the table in batches of whole trial groups (ev: events around the k_vmap launches of the first batch)
+static void vmap_launch(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int32_t n_wav,
+                        hipEvent_t ev0, hipEvent_t ev1) {
+  prom::VmDev& vm = ctx->vm;
+  const prom::ObsDev& ob = ctx->obs;
+  const int32_t n_chunks = prom::vm_chunks(ob.n_pix), n_groups = prom::vm_groups(vm.n_trial);
+  const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, vm.n_orb, n_chunks, n_groups);
+  const int32_t nb_max = std::min(bg * prom::kVmTrials, vm.n_trial);
+  vm.part.ensure(sizeof(double) * (size_t)prom::vm_part_doubles(vm.n_orb, nb_max, n_chunks));
+  static const bool debug = std::getenv("PROM_DEBUG") != nullptr;
+  if (debug)
+    std::fprintf(stderr, "prom: velocity map: %d trials in %d groups, %d batches of up to %d groups, %d chunks\n",
+                 vm.n_trial, n_groups, (n_groups + bg - 1) / bg, bg, n_chunks);
+  for (int32_t g = 0; g < n_groups; g += bg) {
+    const int32_t j_first = prom::vm_group_first(g), nb = std::min(nb_max, vm.n_trial - j_first);
+    prom::launch_vmap(st, wav, vm.q.as<double>(), R, n_wav, ob.lam.as<double>(), ob.sig.as<double>(), ob.k,
+                      ob.data.as<double>(), ob.ivar.as<double>(), vm.F.as<double>(), ob.n_pix, vm.n_orb, vm.n_trial,
+                      j_first, nb, vm.part.as<double>(), g == 0 ? ev0 : nullptr, g == 0 ? ev1 : nullptr);
+    prom::launch_vmap_reduce(st, vm.part.as<double>(), ob.n_pix, vm.n_orb, vm.n_trial, j_first, nb,
+                             vm.mom.as<double>(), vm.n_used.as<int64_t>());
+  }
+}
+
+// the shared tail of the two map calls: q of the whole grid, the batches and the copies back, on stream st
+static void vmap_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, double* mom_out,
+                    int64_t* n_used_out) {
+  prom::VmDev& vm = ctx->vm;
+  const int64_t n = (int64_t)vm.n_orb * vm.n_trial;
+  if (ctx->obs.n_pix == 0) {   // no pixel is used: every moment 0
+    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
+    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
+    return;
+  }
+  const double nan = std::nan("");
+  vm.q.ensure(sizeof(double) * (size_t)n_wav);
+  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, vm.q.as<double>());
+  vmap_launch(ctx, st, wav, R, (int32_t)n_wav, nullptr, nullptr);
+  vm.last_wav = wav;
+  vm.last_R = R;
+  vm.last_n_wav = (int32_t)n_wav;
+  if (mom_out) download(mom_out, vm.mom, 7 * n, st);
+  if (n_used_out) download(n_used_out, vm.n_used, n, st);
+  PROM_HIP(hipStreamSynchronize(st));
+}
+
+static void vmap_check(prom_ctx* ctx, const char* who) {
+  if (!ctx->vm.set || !ctx->obs.set || !ctx->obs.has_data || ctx->obs.n_orb != ctx->vm.n_orb)
+    throw Error(PROM_E_STATE, std::string(who) + ": no trial table on the context (prom_vmap_set; a later "
+                                                 "prom_observe_set or a prom_transit_set with another n_orb drops it)");
+}
+
+int32_t prom_transit_vmap(prom_ctx* ctx, double* mom_out, int64_t* n_used_out) {
+  return guarded(ctx, [&] {
+    prom::TransitDev& tr = ctx->tr;
+    vmap_check(ctx, "prom_transit_vmap");
+    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_vmap: no completed run");
+    if (ctx->vm.n_orb != tr.n_orb) throw Error(PROM_E_STATE, "prom_transit_vmap: the trial table has another n_orb");
+    // the last run's stream orders the map after it
+    vmap_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, mom_out,
+            n_used_out);
+  });
+}
+
+int32_t prom_spectrum_vmap(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                           double* mom_out, int64_t* n_used_out) {
+  return guarded(ctx, [&] {
+    prom::VmDev& vm = ctx->vm;
+    vmap_check(ctx, "prom_spectrum_vmap");
+    PROM_REQUIRE(n_orb == vm.n_orb, "prom_spectrum_vmap: n_orb differs from the trial table's");
+    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_vmap: bad spectrum");
+    for (int64_t w = 0; w < n_wav; ++w)
+      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
+                   "prom_spectrum_vmap: wavelengths must be finite and ascending");
+    const hipStream_t st = ctx->stream;
+    vm.last_wav = vm.last_R = nullptr;   // (the uploads may move the buffers the last map read)
+    upload(vm.wav, wav, n_wav, st);
+    upload(vm.R, R, (int64_t)n_orb * n_wav, st);
+    vmap_on(ctx, st, vm.wav.as<double>(), vm.R.as<double>(), n_wav, mom_out, n_used_out);
+  });
+}
+
+int32_t prom_vmap_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
+  return guarded(ctx, [&] {
+    prom::VmDev& vm = ctx->vm;
+    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_vmap_kernel_ms: bad arguments");
+    if (!vm.set || !ctx->obs.set || !vm.last_wav || ctx->obs.n_pix == 0)
+      throw Error(PROM_E_STATE, "prom_vmap_kernel_ms: no map call to repeat");
+    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
+    const hipStream_t st = ctx->stream;
+    // k_vmap of the first batch (the whole table when it fits the scratch cap), scaled to the table by trial count
+    const int32_t n_groups = prom::vm_groups(vm.n_trial);
+    const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, vm.n_orb, prom::vm_chunks(ctx->obs.n_pix), n_groups);
+    const double scale = (double)vm.n_trial / (double)std::min(bg * prom::kVmTrials, vm.n_trial);
+    double sum = 0.0;
+    for (int32_t r = 0; r < n_runs; ++r) {
+      vmap_launch(ctx, st, vm.last_wav, vm.last_R, vm.last_n_wav, ctx->ev[0], ctx->ev[1]);
+      PROM_HIP(hipStreamSynchronize(st));
+      float ms = 0.0f;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      sum += ms;
+    }
+    *ms_out = scale * sum / n_runs;
   });
 }
 

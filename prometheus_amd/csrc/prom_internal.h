@@ -433,6 +433,19 @@ struct ObsDev {
   int32_t last_n_wav = 0;
 };
 
+// The trial table resident on a context (prom_vmap_set) and the work buffers of the velocity-map calls.
+struct VmDev {
+  bool set = false;
+  int32_t n_orb = 0, n_trial = 0;
+  DevBuf F;                               // [n_orb][n_trial]
+  DevBuf q, part, mom, n_used;            // [n_wav], the batch's partial records, [n_orb][n_trial][7], [n_orb][n_trial]
+  DevBuf wav, R;                          // prom_spectrum_vmap's copies of the caller's spectrum
+  // the last map's spectrum, for prom_vmap_kernel_ms to repeat (null: none yet)
+  const double* last_wav = nullptr;
+  const double* last_R = nullptr;
+  int32_t last_n_wav = 0;
+};
+
 }  // namespace prom
 
 struct prom_ctx {
@@ -446,6 +459,8 @@ struct prom_ctx {
   std::vector<prom::MolTable> mtables;
   prom::TransitDev tr;
   prom::ObsDev obs;
+  prom::VmDev vm;
+  int64_t vmap_scratch_bytes = (int64_t)256 << 20;   // PROM_VMAP_SCRATCH_MB: cap of k_vmap's partial records
   prom::DevBuf scratch[6];
   bool timing = false;
   std::vector<hipEvent_t> tev;   // pool, 4 per timed run
@@ -529,6 +544,14 @@ void launch_observe(hipStream_t s, const double* wav, const double* q, const dou
                     double* num, double* den, hipEvent_t ev0, hipEvent_t ev1);
 void launch_observe_chi2(hipStream_t s, const double* num, const double* den, const double* data, const double* ivar,
                          int32_t n_pix, int32_t n_orb, double* chi2, int64_t* n_used);
+// velocity maps (prom_vmap.hip): the moments of trials [j_first, j_first + nb) of F[n_orb][n_trial] into the batch's
+// partial records part[n_orb][nb][chunks][8], and their sum over the chunks into mom[n_orb][n_trial][7], n_used
+void launch_vmap(hipStream_t s, const double* wav, const double* q, const double* R, int32_t n_wav, const double* lam,
+                 const double* sig, double k, const double* data, const double* ivar, const double* F, int32_t n_pix,
+                 int32_t n_orb, int32_t n_trial, int32_t j_first, int32_t nb, double* part, hipEvent_t ev0,
+                 hipEvent_t ev1);
+void launch_vmap_reduce(hipStream_t s, const double* part, int32_t n_pix, int32_t n_orb, int32_t n_trial,
+                        int32_t j_first, int32_t nb, double* mom, int64_t* n_used);
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

@@ -623,6 +623,31 @@ class _ObserveJob:
                             spectrum=R)
 
 
+class _VmapJob:
+    """One Transit.velocity_map call inside _integrate: the observation and the trial table go to the device once
+    each while their content keys are unchanged, then the map runs over the (one) chunk's R."""
+
+    def __init__(self, observation, factors):
+        self.obs = _ObserveJob(observation, False)
+        self.F = factors
+        self.key = (observation.key,) + _content_fingerprint(factors)
+        self.whole = False
+        self.moments = self.n_used = None
+
+    def upload(self, dev) -> None:
+        self.obs.upload(dev)
+        if dev.vmap_key != self.key:
+            dev.vmap_set(self.F, key=self.key)
+
+    def run(self, dev, wavelength, a: int, b: int):
+        if not self.whole:   # (velocity_map refuses such a run before it starts)
+            raise RuntimeError("velocity_map: the run was split into wavelength shards or chunks")
+        return dev.transit_vmap()
+
+    def add(self, part) -> None:
+        self.moments, self.n_used = part
+
+
 _STAR_TABLES: "weakref.WeakKeyDictionary" = None
 
 
@@ -846,6 +871,57 @@ class Transit:
         R, _ = self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=return_spectrum, observe=job)
         return job.result(obs, R)
 
+    def velocity_map(self, observation, factors, devices: Optional[Sequence[int]] = None,
+                     max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0):
+        """Run the transit and map it against data over a table of trial frames on the device: ``observation`` is an
+        observation.Observation with data and err (its own frame_shifts are not applied), ``factors`` the table
+        F[n_orb][n_trial] of frame factors (observation.trial_factors, observation.kp_vsys_factors).  R stays in
+        device memory; per (phase, trial) the seven moments of model against data come back (7 doubles and a count)
+        as an observation.VelocityMap, which forms chi-square, chi-square with a free scale, the weighted
+        cross-correlation and a log-likelihood from them.  The observation and the table are uploaded once each while
+        their content is unchanged.
+
+        The moments are not additive over wavelength partials (M = num / den needs every shard's sums before it meets
+        the data), so the run must be one wavelength shard on one device in one chunk: otherwise ValueError, before
+        anything is uploaded or run.  ``devices``: one GPU id (default 0); ``max_memory_gb`` (default 2) bounds the
+        chunk as in sumOverChords."""
+        from . import observation as obs
+        if not isinstance(observation, obs.Observation):
+            raise TypeError("velocity_map: observation must be an observation.Observation")
+        if observation.data is None:
+            raise ValueError("velocity_map: the Observation has no data (give data and err): the moments compare "
+                             "the model with data")
+        F = np.ascontiguousarray(np.asarray(factors, dtype=np.float64))
+        n_orb = len(self.spatialGrid.constructOrbphaseAxis())
+        if observation.n_orb != n_orb:
+            raise ValueError("velocity_map: the Observation has %d phases, the transit %d" % (observation.n_orb, n_orb))
+        if F.ndim != 2 or F.shape[0] != n_orb or F.shape[1] < 1:
+            raise ValueError("velocity_map: factors must be [n_orb][n_trial] with n_orb = %d" % n_orb)
+        if not (np.all(np.isfinite(F)) and np.all(F > 0)):
+            raise ValueError("velocity_map: factors must be finite and positive")
+        if not hasattr(self, "wavelength"):
+            self.addWavelength()
+        devices = [0] if devices is None else list(devices)
+        max_memory_gb = 2.0 if max_memory_gb is None else max_memory_gb
+        n_wav, chunk = len(self.wavelength), self._wavelength_chunk(max_memory_gb, n_orb)
+        if len(devices) != 1 or n_wav > chunk:
+            raise ValueError(
+                "velocity_map: the run would be split into %d wavelength shard(s) and chunks of %d wavelengths (the "
+                "grid has %d); the moments are not additive over wavelength partials (the model M = num / den needs "
+                "the sums of the whole grid before it meets the data).  Give one device and raise max_memory_gb "
+                "until the grid fits one chunk, or observe per trial with Transit.observe, which combines partials."
+                % (len(devices), chunk, n_wav))
+        job = _VmapJob(observation, F)
+        self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
+        return obs.VelocityMap(job.moments, job.n_used, F)
+
+    def _wavelength_chunk(self, max_memory_gb, n_orb: int) -> int:
+        """Wavelengths per device step under ``max_memory_gb``."""
+        n_atoms = sum(1 for d in self.atmosphere.densityDistributionList for c in d.constituents
+                      if not c.isMolecule)
+        per_wav = 8 * n_orb * (2 + max(1, n_atoms))
+        return max(4096, int(max_memory_gb * 1e9) // per_wav) // WAVE_ALIGN * WAVE_ALIGN
+
     def _integrate(self, max_memory_gb, devices, cull_tau, options, bounds, want_R=True, observe=None):
         if not hasattr(self, "wavelength"):
             self.addWavelength()
@@ -857,10 +933,7 @@ class Transit:
                 raise _native.NativeUnavailable("no HIP device visible")
             devices = list(range(min(avail, max(1, n_wav // 65536))))
         devices = list(devices)
-        n_atoms = sum(1 for d in self.atmosphere.densityDistributionList for c in d.constituents
-                      if not c.isMolecule)
-        per_wav = 8 * n_orb * (2 + max(1, n_atoms))
-        chunk = max(4096, int(max_memory_gb * 1e9) // per_wav) // WAVE_ALIGN * WAVE_ALIGN
+        chunk = self._wavelength_chunk(max_memory_gb, n_orb)
         R = None
         if want_R:
             # one chunk on one device: R lands in page-locked memory from the library's pool in one DMA

@@ -133,6 +133,104 @@ def planet_frame_shifts(planet, orbphase) -> np.ndarray:
     return lightcurve.planet_shifts(planet, orbphase)
 
 
+def trial_factors(base, velocities) -> np.ndarray:
+    """Trial table F[n_orb][n_trial] = base[:, None] * calculateDopplerShift(velocities)[None, :]: every phase's own
+    frame factor ``base`` [n_orb] (e.g. planet_frame_shifts; None: ones, with one row) scanned over a grid of trial
+    line-of-sight velocities [cm/s]."""
+    from . import constants as const
+    d = const.calculateDopplerShift(np.asarray(velocities, dtype=np.float64).reshape(-1))
+    b = np.ones(1) if base is None else np.asarray(base, dtype=np.float64).reshape(-1)
+    return np.ascontiguousarray(b[:, None] * d[None, :])
+
+
+def kp_vsys_factors(orbphase, Kp, Vsys) -> np.ndarray:
+    """Trial table F[n_orb][nKp * nVsys], Kp-major, of a (Kp, Vsys) grid [cm/s]:
+    calculateDopplerShift(-Kp_i sin(orbphase_o) + Vsys_l), Planet.getLOSvelocity's convention.  With
+    Kp = [sqrt(G M_star / a)] and Vsys = [0] it is planet_frame_shifts bit for bit."""
+    from . import constants as const
+    orb = np.asarray(orbphase, dtype=np.float64).reshape(-1)
+    kp = np.asarray(Kp, dtype=np.float64).reshape(-1)
+    vs = np.asarray(Vsys, dtype=np.float64).reshape(-1)
+    v = (-np.sin(orb))[:, None, None] * kp[None, :, None] + vs[None, None, :]
+    return np.ascontiguousarray(const.calculateDopplerShift(v).reshape(len(orb), len(kp) * len(vs)))
+
+
+def _ratio(a, b):
+    """a / b, NaN where b == 0."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(b == 0.0, np.nan, a / np.where(b == 0.0, 1.0, b))
+
+
+class VelocityMap:
+    """Result of Transit.velocity_map: ``moments`` [n_orb][n_trial][7] and ``n_used`` [n_orb][n_trial] of the model in
+    every trial frame against the data (include/prom_hip.h, "velocity maps on the device"; m0 = sum iv,
+    m1 = sum iv M, m2 = sum iv d, m3 = sum iv M^2, m4 = sum iv M d, m5 = sum iv d^2, m6 = sum iv (M - d)^2 over the
+    used pixels) and the table ``factors`` they belong to.  The statistics are per (phase, trial), NaN where their
+    denominator is 0."""
+
+    STATS = ("chi2", "chi2_scaled", "scale", "ccf", "loglike")
+
+    def __init__(self, moments, n_used, factors):
+        self.moments = np.asarray(moments, dtype=np.float64)
+        self.n_used = np.asarray(n_used, dtype=np.int64)
+        self.factors = np.asarray(factors, dtype=np.float64)
+        if self.moments.ndim != 3 or self.moments.shape[2] != 7 or self.n_used.shape != self.moments.shape[:2]:
+            raise ValueError("VelocityMap: moments must be [n_orb][n_trial][7] and n_used [n_orb][n_trial]")
+
+    def _m(self, i):
+        return self.moments[..., i]
+
+    @property
+    def chi2(self):
+        """sum iv (M - d)^2: m6."""
+        return self._m(6)
+
+    @property
+    def scale(self):
+        """The scale a that minimises sum iv (a M - d)^2: m4 / m3."""
+        return _ratio(self._m(4), self._m(3))
+
+    @property
+    def chi2_scaled(self):
+        """The minimum over a of sum iv (a M - d)^2: m5 - m4^2 / m3."""
+        return self._m(5) - _ratio(self._m(4) * self._m(4), self._m(3))
+
+    @property
+    def ccf(self):
+        """Weighted cross-covariance sum iv (M - <M>)(d - <d>) with weighted means: m4 - m1 m2 / m0."""
+        return self._m(4) - _ratio(self._m(1) * self._m(2), self._m(0))
+
+    @property
+    def loglike(self):
+        """Brogi & Line (2019) with inverse-variance weights: N = n_used, s_f^2 = (m5 - m2^2 / m0) / m0,
+        s_g^2 = (m3 - m1^2 / m0) / m0, C = ccf / m0; logL = -N / 2 ln(s_f^2 - 2 C + s_g^2)."""
+        m0, m1, m2, m3, m5 = (self._m(i) for i in (0, 1, 2, 3, 5))
+        sf = _ratio(m5 - _ratio(m2 * m2, m0), m0)
+        sg = _ratio(m3 - _ratio(m1 * m1, m0), m0)
+        c = _ratio(self.ccf, m0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return -0.5 * self.n_used * np.log(sf - 2.0 * c + sg)
+
+    def _stat(self, stat):
+        if isinstance(stat, str):
+            if stat not in self.STATS:
+                raise ValueError("VelocityMap: unknown statistic %r (one of %s)" % (stat, ", ".join(self.STATS)))
+            return getattr(self, stat)
+        return np.asarray(stat, dtype=np.float64)
+
+    def total(self, stat="chi2"):
+        """The statistic (a name or an array [n_orb][n_trial]) summed over the phases: [n_trial]."""
+        return self._stat(stat).sum(axis=0)
+
+    def grid(self, stat, n_kp: int, n_vsys: int):
+        """A Kp-major statistic ([..., nKp * nVsys], e.g. over a kp_vsys_factors table) as [..., nKp, nVsys]."""
+        s = self._stat(stat)
+        if s.shape[-1] != n_kp * n_vsys:
+            raise ValueError("VelocityMap.grid: %d trials are no %d x %d grid" % (s.shape[-1], n_kp, n_vsys))
+        return s.reshape(s.shape[:-1] + (n_kp, n_vsys))
+
+
 class Observed:
     """Result of Transit.observe, in the caller's pixel order: ``model`` [n_orb][n_pix] (None when not asked),
     ``coverage`` = den / (sigma sqrt(2 pi) erf(k / sqrt 2)) (1 where the grid covers a pixel's support densely, less
