@@ -632,6 +632,8 @@ int32_t prom_transit_set(prom_ctx* ctx, const prom_transit_problem* pb) {
       tr.env_fork = fk ? (std::atoi(fk) != 0 ? 1 : 0) : -1;
       const char* sgs = std::getenv("PROM_SIG_STAGGER");
       tr.env_stagger = sgs && std::atoi(sgs) != 0;
+      const char* csp = std::getenv("PROM_COL_SPEC");
+      tr.col_spec = !(csp && std::atoi(csp) == 0);
     }
     PROM_REQUIRE(pb->n_pr < (1 << 24), "transit: n_pr must be < 2^24");
     tr.terms.clear();
@@ -1402,6 +1404,11 @@ int32_t prom_transit_set(prom_ctx* ctx, const prom_transit_problem* pb) {
                      n_atoms, tr.n_sig_fb, tr.n_sig_fb_tc, (long long)cnt[0], (long long)cnt[1], (long long)cnt[2],
                      (long long)cnt[5], (long long)cnt[6], tr.sig_deg);
       }
+    }
+    if (std::getenv("PROM_DEBUG")) {
+      const prom::ColPlan cp = prom::col_plan(tr);
+      std::fprintf(stderr, "[prom] column chain: transmission curves %d, phase partials %d, column kernel kind %d "
+                   "(0: generic)\n", cp.tcp ? 1 : 0, cp.partials ? 1 : 0, cp.kind);
     }
     PROM_HIP(hipStreamSynchronize(s));
     if (seg_key_new) {

@@ -418,11 +418,12 @@ __device__ __forceinline__ T wave_suffix(T v, Op op) {
 // numpy.heaviside(d, 1.0)
 __device__ __forceinline__ double heaviside1(double d) { return d < 0.0 ? 0.0 : (d >= 0.0 ? 1.0 : d); }
 
-// One density sample, in the reference's evaluation order (see prom_density_kind in prom_hip.h).
-__device__ __forceinline__ double density_at(const DensityDev& m, double xv, double y, double z,
-                                             double bx, double by) {
+// One density sample, in the reference's evaluation order (see prom_density_kind in prom_hip.h).  `kind` is the
+// model's kind: a caller that knows it at compile time passes the constant and the switch folds to one case.
+__device__ __forceinline__ double density_kind(int32_t kind, const DensityDev& m, double xv, double y, double z,
+                                               double bx, double by) {
   const double dx = xv - bx, dy = y - by;
-  switch (m.kind) {
+  switch (kind) {
     case PROM_DENSITY_BAROMETRIC: {
       const double r = sqrt((dx * dx + dy * dy) + z * z);
       return (m.p[0] * exp((m.p[1] - r) / m.p[2])) * heaviside1(r - m.p[1]);
@@ -459,6 +460,10 @@ __device__ __forceinline__ double density_at(const DensityDev& m, double xv, dou
     default:
       return __builtin_nan("");
   }
+}
+__device__ __forceinline__ double density_at(const DensityDev& m, double xv, double y, double z,
+                                             double bx, double by) {
+  return density_kind(m.kind, m, xv, y, z, bx, by);
 }
 
 // numpy pairwise_sum of (a[i] * chi) for i < n (numpy/_core/src/umath/loops_utils.h.src),

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/prom_hip.h"
+#include "tc_phase.h"
 
 namespace prom {
 
@@ -165,14 +166,9 @@ struct SigSeg {
   double xs, inv;
 };
 
-// Per molecular slot of a transit problem.
-// Per 32-chord group of one phase (k_columns8, transmission-curve path): the order-independent phase sums
-// k_tc_build needs before its node sums (max / min of the active finite columns, chord counts by class)
-struct TcPart {
-  double nmax, nmin;
-  int32_t nact, ntr, nbl, nnf;
-};
+// (TcPart, the per 32-chord group partial of k_columns8: tc_phase.h)
 
+// Per molecular slot of a transit problem.
 struct MolSlotDev {
   const double* P;       // [n_p] dyn cm^-2
   const double* T;       // [n_t]
@@ -404,7 +400,8 @@ struct TransitDev {
   DevBuf tc_const;                          // k_tc_build constants: Chebyshev matrix [kTcD][kTcD], node factors [kTcD]
   int32_t tc_parts = 1;
   double tc_fsum = 0.0;                     // sum of the chords' F_out (every phase's disk sum; per set)
-  bool tc_pp_ok = false;                    // this run's k_columns8 wrote the curves' phase partials (launch_transit)                     // chord parts per (phase, chain) of k_tc_build
+  bool tc_pp_ok = false;                    // this run's k_columns8 wrote the curves' phase partials (launch_transit)
+  bool col_spec = true;                     // k_columns8's one-term, one-analytic-kind instances (PROM_COL_SPEC=0, per set)
   double tc_ybound = 0.0;
   RunSlot slot[kMaxSlots];
   // PROM_GRAPH=1: a fast-path run is one hipGraph per slot, captured at the slot's first untimed run
@@ -497,6 +494,15 @@ void launch_molecular_sigma(hipStream_t s, const MolTable& t, int64_t n_chords, 
 // tau pair (the fast path carries them on the tau kernel's dispatch packet)
 void launch_transit(hipStream_t s, TransitDev& tr, RunSlot& rs, const std::vector<AtomTable>& tables,
                     const std::vector<MolTable>& mtables, hipEvent_t* ev, int* variant, bool stage_events);
+// which column kernel a run takes and what follows it (prom_transit.hip): the windowed-path and k_columns8
+// predicates, resampled sigma, species merging, species and terms downstream of it; tcp: the transmission-curve path,
+// partials: k_columns8 writes the phase partials, kind: the density kind of its one-term instance (0: generic)
+struct ColPlan {
+  bool wpath, cols8, pre_sigma, msp, tcp, partials;
+  int32_t na, n_terms;
+  int kind;
+};
+ColPlan col_plan(const TransitDev& tr);
 // orbital Doppler shift: the per-phase cross-section rows, Y or sigma_s, and the Q ranges (prom_sigma.hip)
 void launch_sigma_rows(hipStream_t s, int32_t nsig, const SigTabs4& tabv, const double* wav, int64_t n_wav,
                        int32_t n_rows, const SigSeg* seg, const int32_t* fb, int32_t n_fb, double* sig, float4* tq,

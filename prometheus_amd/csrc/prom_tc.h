@@ -6,20 +6,11 @@
 
 namespace prom {
 
-constexpr double kTcEps = 0x1p-7;        // tail threshold of q
-constexpr int kTcExpEps = -7;            // its binary exponent
-constexpr double kTcSat = 40.0;          // tau above which a chord is opaque (e^-40 = 4e-18)
+// (kTcEps, the tail threshold of q, its binary exponent kTcExpEps, kTcSat and tc_octaves: tc_phase.h)
 
 // q = Y N_max's binary exponent (q normal and >= 2^-7)
 __device__ __forceinline__ int32_t tc_exponent(double q) {
   return (int32_t)((__builtin_bit_cast(unsigned long long, q) >> 52) & 0x7ff) - 1023;
-}
-
-// octaves [0, L) that cover q in [eps, qhi]: 0 when qhi < eps, INT32_MAX when not finite
-__device__ __forceinline__ int32_t tc_octaves(double qhi) {
-  if (!(qhi >= kTcEps)) return 0;
-  if (!(qhi <= 1.0e300)) return 0x7fffffff;
-  return tc_exponent(qhi) - kTcExpEps + 1;
 }
 
 // the octave's Chebyshev series at q (normal, inside the table): v = log2 of q's mantissa in [0, 1), Clenshaw in

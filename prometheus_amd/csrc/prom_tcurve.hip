@@ -197,20 +197,10 @@ __global__ void __launch_bounds__(kTcB2) k_tc_build(const int32_t* __restrict__ 
   }
   if (tcp) fs = fsum_set;
   // table extent: octaves up to the host's bound of q = Y N_max, or up to q = 40 N_max / N_min (every chord
-  // opaque beyond it), whichever comes first; lg caps it
-  const bool fin = nnf == 0 && nmax > 0.0 && nact > 0;
-  int32_t L = 0, top_opaque = 0, trunc = 0;
-  if (fin) {
-    const int32_t L1 = ybound > 0.0 ? tc_octaves(ybound * nmax * (1.0 + 0x1p-40)) : 0x7fffffff;
-    const int32_t L2 = tc_octaves(kTcSat * (nmax / nmin));
-    if (L2 <= L1 && L2 <= lg) {
-      L = L2;
-      top_opaque = 1;
-    } else {
-      L = L1 < lg ? L1 : lg;
-      trunc = L1 > lg ? 4 : 0;   // (the lookups may need the exact sum beyond the table: header flag 4)
-    }
-  }
+  // opaque beyond it), whichever comes first; lg caps it (tc_phase.h, shared with the host test)
+  int32_t fin_i, L, top_opaque, trunc;
+  tc_phase_extent(nmax, nmin, nact, nnf, ybound, lg, &fin_i, &L, &top_opaque, &trunc);
+  const bool fin = fin_i != 0;
   const int32_t j0 = ch * kTcChain;
 #ifdef PROM_TRACE
   if (tid == 0) {

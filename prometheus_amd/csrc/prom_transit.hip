@@ -134,7 +134,10 @@ using ScDev = ScDevHost;
 // lanes 0..7 form numpy's eight pairwise partial sums, lane 0 combines them (loops_utils.h.src order)
 // -> N = (0.0 + pairwise_x(n chi)) * delta_x exactly as gasProperties.py:940.  The k_ntot + k_columns
 // pair handles molecular terms and n_x > 64.
-template <int SPL, int NSIG>
+// KIND > 0 (the transmission-curve path's common case): one term whose scenario has the analytic density KIND -- the
+// term loop is one copy and density_kind's switch folds to that case; the arithmetic per sample is unchanged.
+// KIND == 0: any terms and densities.
+template <int SPL, int NSIG, int KIND = 0>
 __global__ void __launch_bounds__(kBlock) k_columns8(const ColArgs ca, int32_t n_terms,
                                  const double* __restrict__ x, int32_t n_x,
                                  int32_t n_pr, int32_t n_orb, double delta_x, const double* __restrict__ cy,
@@ -147,6 +150,7 @@ __global__ void __launch_bounds__(kBlock) k_columns8(const ColArgs ca, int32_t n
                                  double* __restrict__ sig, float4* __restrict__ tq, int32_t merge_sp,
                                  double nscale_m, int32_t* __restrict__ hcnt, uint8_t* __restrict__ zfl,
                                  int32_t sig_rows, TcPart* __restrict__ tcp) {
+  static_assert(KIND == 0 || NSIG == 0, "the one-kind instances run without sigma workgroups");
   if (hcnt && blockIdx.x == 0 && threadIdx.x < 2) hcnt[threadIdx.x] = 0;   // k_order's heavy-entry counters
   // Eight lanes per chord; lane j holds samples j, j + 8, ..., j + 8 (SPL - 1).  That is numpy's
   // pairwise_sum layout (loops_utils.h.src) for 8 <= n_x < 128: lane j accumulates r[j] = a[j] +
@@ -256,8 +260,8 @@ __global__ void __launch_bounds__(kBlock) k_columns8(const ColArgs ca, int32_t n
   double nv[SPL];
   int32_t cur_sc = -1;
 #pragma unroll
-  for (int32_t t = 0; t < 8; ++t) {
-    if (t >= n_terms) break;
+  for (int32_t t = 0; t < (KIND > 0 ? 1 : 8); ++t) {
+    if (KIND == 0 && t >= n_terms) break;
     const TermDev td = ca.t[t];
     if (td.scenario != cur_sc) {   // one density evaluation per scenario, shared by its constituents
       cur_sc = td.scenario;
@@ -267,9 +271,13 @@ __global__ void __launch_bounds__(kBlock) k_columns8(const ColArgs ca, int32_t n
       for (int k = 0; k < SPL; ++k) {
         const int32_t i = gl + 8 * k;
         nv[k] = 0.0;
-        if (valid && !blocked && i < n_x)
-          nv[k] = sc.m.kind == PROM_DENSITY_GRIDDED ? grid_density(sc.m, sc.tab, xs[k], y, z, bxo, byo)
-                  : sc.tab ? sc.tab[((int64_t)ip * n_orb + o) * n_x + i] : density_at(sc.m, xs[k], y, z, bxo, byo);
+        if (valid && !blocked && i < n_x) {
+          if constexpr (KIND > 0)
+            nv[k] = density_kind(KIND, sc.m, xs[k], y, z, bxo, byo);
+          else
+            nv[k] = sc.m.kind == PROM_DENSITY_GRIDDED ? grid_density(sc.m, sc.tab, xs[k], y, z, bxo, byo)
+                    : sc.tab ? sc.tab[((int64_t)ip * n_orb + o) * n_x + i] : density_at(sc.m, xs[k], y, z, bxo, byo);
+        }
       }
     }
     double av[SPL];
@@ -2191,22 +2199,50 @@ static void kp_rec(TransitDev& tr, int id, bool stop, hipStream_t s) {
   PROM_HIP(hipEventRecord(tr.kprof[2 * id + (stop ? 1 : 0)], s));
 }
 
+// The density kind k_columns8 may be compiled for (its KIND > 0 instances): one term whose scenario's density is
+// analytic -- evaluated by density_kind, neither tabulated nor gridded; 0: the generic instance
+static int col_spec_kind(const TransitDev& tr, const ColArgs& cargs, int32_t n_terms) {
+  if (!tr.col_spec || n_terms != 1) return 0;
+  const ScDevHost& sc = cargs.sc[cargs.t[0].scenario & 3];
+  if (sc.tab) return 0;
+  const int k = sc.m.kind;
+  return (k == PROM_DENSITY_BAROMETRIC || k == PROM_DENSITY_HYDROSTATIC || k == PROM_DENSITY_POWERLAW ||
+          k == PROM_DENSITY_TORUS) ? k : 0;
+}
+
+// Which column kernel a run takes and what follows it: computed here once, for launch_transit and for
+// prom_transit_set's PROM_DEBUG line
+ColPlan col_plan(const TransitDev& tr) {
+  ColPlan p{};
+  p.wpath = tr.exp_mode && tr.n_mol == 0 && tr.n_atoms >= 1 && tr.n_atoms <= kWinMaxSpecies;
+  p.cols8 = tr.n_mol == 0 && tr.n_x <= 64 && tr.n_terms <= 8 && tr.n_sc <= 4;
+  p.pre_sigma = p.cols8 && p.wpath && tr.window && !tr.star;
+  p.msp = p.pre_sigma && tr.species_merge_ok;
+  p.na = p.msp ? 1 : tr.n_atoms;
+  p.n_terms = p.msp ? 1 : tr.n_terms;
+  p.tcp = tr.tcurve && p.cols8 && p.wpath && tr.window && !tr.star && p.na == 1 && tr.sig_seg_ok;
+  p.partials = p.tcp && tr.n_pr % 32 == 0 && p.n_terms == 1;
+  p.kind = p.tcp ? col_spec_kind(tr, p.msp ? tr.colargs_m : tr.colargs, p.n_terms) : 0;
+  return p;
+}
+
 void launch_transit(hipStream_t s, TransitDev& tr, RunSlot& rs, const std::vector<AtomTable>& tables,
                     const std::vector<MolTable>& mtables, hipEvent_t* ev, int* variant, bool stage_events) {
   const int64_t per = (int64_t)tr.n_orb * tr.n_pr * tr.n_x;
-  const bool wpath = tr.exp_mode && tr.n_mol == 0 && tr.n_atoms >= 1 && tr.n_atoms <= kWinMaxSpecies;
+  const ColPlan cplan = col_plan(tr);
+  const bool wpath = cplan.wpath;
   // sigma_s(shift lambda_w) is resampled by extra workgroups of the column kernel (they run beside the
   // chord work): once per wavelength without orbital Doppler shift, once per (phase, wavelength) with it
-  const bool cols8 = tr.n_mol == 0 && tr.n_x <= 64 && tr.n_terms <= 8 && tr.n_sc <= 4;
-  const bool pre_sigma = cols8 && wpath && tr.window && !tr.star;
+  const bool cols8 = cplan.cols8;
+  const bool pre_sigma = cplan.pre_sigma;
   const int32_t sig_rows = tr.uniform_shift ? 1 : tr.n_orb;
   // species merging (TransitDev::species_merge_ok) on the resampled fast path: downstream of the
   // column kernel there is one effective absorber
-  const bool msp = pre_sigma && tr.species_merge_ok;
+  const bool msp = cplan.msp;
   const int32_t nsig = tr.n_atoms;                 // species the column kernel resamples
-  const int32_t na = msp ? 1 : tr.n_atoms;         // species the ordering and tau kernels see
+  const int32_t na = cplan.na;                     // species the ordering and tau kernels see
   const ColArgs& cargs = msp ? tr.colargs_m : tr.colargs;
-  const int32_t n_terms = msp ? 1 : tr.n_terms;
+  const int32_t n_terms = cplan.n_terms;
   const double* smax = msp ? tr.sigma_max_m.as<double>() : tr.sigma_max_dev.as<double>();
   const SigTabs4& tabs4 = msp ? tr.sigtab_m : tr.sigtab_v;
   *variant = (na <= 4 ? na : 0) + (tr.exp_mode ? (wpath && tr.window ? 20 : 10) : 0);
@@ -2223,8 +2259,8 @@ void launch_transit(hipStream_t s, TransitDev& tr, RunSlot& rs, const std::vecto
   // 1. densities -> column densities -> blocking/transparency flags
   const int64_t nc = (int64_t)tr.n_orb * tr.n_pr;
   bool sig_after_order = false;   // Doppler sigma rows still to queue, after k_order (rs.sig_late)
-#define PROM_COLS(SV, NSV)                                                                               \
-  hipExtLaunchKernelGGL((k_columns8<SV, NSV>),                                                           \
+#define PROM_COLS(SV, NSV, KV)                                                                           \
+  hipExtLaunchKernelGGL((k_columns8<SV, NSV, KV>),                                                       \
                      dim3(col_blocks),                                                                    \
                      dim3(kBlock), 0, s, kp_start(tr, PROM_K_COLUMNS, ev0), kp_stop(tr, PROM_K_COLUMNS, nullptr), 0, \
                      cargs, n_terms,                                                                      \
@@ -2235,20 +2271,28 @@ void launch_transit(hipStream_t s, TransitDev& tr, RunSlot& rs, const std::vecto
                      rs.flags.as<int32_t>(), tr.sigtab_v, tr.wav.as<double>(), tr.n_wav, rs.sig.as<double>(), \
                      pre_sigma ? rs.tq.as<float4>() : nullptr, msp ? 1 : 0, tr.sigtab_m.t[0].nscale,    \
                      (pre_sigma && tr.plan) ? rs.hcnt.as<int32_t>() : nullptr, rs.zfl.as<uint8_t>(), sig_rows, col_tcp)
-#define PROM_COLS_L(NSV)                       \
-  if (tr.n_x <= 8) PROM_COLS(1, NSV);          \
-  else if (tr.n_x <= 16) PROM_COLS(2, NSV);    \
-  else if (tr.n_x <= 32) PROM_COLS(4, NSV);    \
-  else PROM_COLS(8, NSV);
+#define PROM_COLS_K(NSV, KV)                       \
+  if (tr.n_x <= 8) PROM_COLS(1, NSV, KV);          \
+  else if (tr.n_x <= 16) PROM_COLS(2, NSV, KV);    \
+  else if (tr.n_x <= 32) PROM_COLS(4, NSV, KV);    \
+  else PROM_COLS(8, NSV, KV);
+#define PROM_COLS_L(NSV) PROM_COLS_K(NSV, 0)
   // transmission-curve path (prom_tcurve.hip, the default for one effective absorber): k_columns8, then
   // k_tc_build -> k_sigma_tc; no ordering, windows or heavy entries
-  const bool tcp = tr.tcurve && cols8 && wpath && tr.window && !tr.star && na == 1 && tr.sig_seg_ok;
+  const bool tcp = cplan.tcp;
   TcPart* col_tcp = nullptr;   // the curves' phase partials (k_columns8 -> k_tc_build)
   if (tcp) {
-    if (tr.n_pr % 32 == 0 && n_terms == 1) col_tcp = rs.tc_pp.as<TcPart>();
+    if (cplan.partials) col_tcp = rs.tc_pp.as<TcPart>();
     tr.tc_pp_ok = col_tcp != nullptr;
     const unsigned col_blocks = (unsigned)((nc + kBlock / 8 - 1) / (kBlock / 8));
-    PROM_COLS_L(0)
+    // one term of one analytic density kind: the instance compiled for that kind (PROM_COL_SPEC=0: the generic one)
+    switch (cplan.kind) {
+      case PROM_DENSITY_BAROMETRIC: PROM_COLS_K(0, PROM_DENSITY_BAROMETRIC) break;
+      case PROM_DENSITY_HYDROSTATIC: PROM_COLS_K(0, PROM_DENSITY_HYDROSTATIC) break;
+      case PROM_DENSITY_POWERLAW: PROM_COLS_K(0, PROM_DENSITY_POWERLAW) break;
+      case PROM_DENSITY_TORUS: PROM_COLS_K(0, PROM_DENSITY_TORUS) break;
+      default: PROM_COLS_L(0) break;
+    }
     PROM_HIP(hipGetLastError());
     // stats runs: {columns start, tables done, sigma start, sigma done}; timed runs: the sigma kernel's
     // interval opens at the table kernel's completion
@@ -2327,6 +2371,7 @@ void launch_transit(hipStream_t s, TransitDev& tr, RunSlot& rs, const std::vecto
     kp_rec(tr, PROM_K_COLUMNS, true, s);
   }
 #undef PROM_COLS_L
+#undef PROM_COLS_K
 #undef PROM_COLS
   if (tr.star) {
     // 2'. stellar spectrum: one exact chord-order kernel over the flags / columns
