@@ -253,7 +253,9 @@ int32_t prom_transit_result(prom_ctx* ctx, double* R_out);
 int32_t prom_host_alloc(int64_t bytes, void** out);
 /* Return a prom_host_alloc buffer to the pool (PROM_E_ARG for any other pointer). */
 int32_t prom_host_free(void* p);
-/* Column densities N[s][o][ip] of the last run (atomic constituents in scenario order); testing aid. */
+/* Column densities N[s][o][ip] of the last run (atomic constituents in scenario order); testing aid.  With the species
+ * merged into one effective absorber (tau_kernel_variant's units digit 1 for several atomic constituents) only slot 0
+ * is written, and it holds the chi = 1 column. */
 int32_t prom_transit_columns(prom_ctx* ctx, double* N_out);
 
 /* Band statistics of the last run's R on the device, for light curves (the band-averaged transit
