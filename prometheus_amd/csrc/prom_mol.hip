@@ -68,16 +68,24 @@ __device__ __forceinline__ double acc_exp1024_e(double acc, double F, double y, 
 }
 
 // G of one slot: per P interval i in [0, n_p - 2] and lambda' interval w, 32 bytes {g_i, s_i, g_{i+1} - g_i,
-// s_{i+1} - s_i} with g_i = g(i, w), s_i = g(i, w + 1) - g(i, w), at the slot's T (unused when T is outside the
+// s_{i+1} - s_i} with g_i = g(i, w), s_i = g(i, w + 1) - g(i, w), at the slot's T (zeros when T is outside the
 // table), so a sample's bilinear value g_i + t_w s_i + t_p ((g_{i+1} - g_i) + t_w (s_{i+1} - s_i)) is three FMAs
 // from one 32-byte record (two 16-byte loads)
 __global__ void k_mol_gt(const double* __restrict__ Tg, int32_t n_t, double T, const double* __restrict__ V,
                          int32_t n_p, int64_t n_w, double2* __restrict__ G) {
   int64_t it = 0;
   double tt = 0.0;
-  if (!rgi_bracket(Tg, n_t, T, &it, &tt)) return;
   const int64_t nw1 = n_w - 1;
   const int64_t tot = (int64_t)(kMolBilin ? max(n_p - 1, 1) : n_p) * nw1;
+  if (!rgi_bracket(Tg, n_t, T, &it, &tt)) {
+    // T outside the table: zero records.  k_tau_mol applies the slot's out-of-table mask as a product, 0 f(G), which is
+    // the reference's sigma = 0 only for finite f: the buffer is reused from set to set and may hold an earlier
+    // problem's records, whose 2^(y / 1024) can overflow
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < (kMolBilin ? 2 : 1) * tot;
+         k += (int64_t)gridDim.x * blockDim.x)
+      G[k] = make_double2(0.0, 0.0);
+    return;
+  }
   // stored as y = 1024 log2(10) v (the lookups' exponent scale: 10^v = 2^(y/1024), no multiply per sample)
   auto y = [&](int64_t i, int64_t w) {
     const double* v0 = V + (i * n_t + it) * n_w + w;

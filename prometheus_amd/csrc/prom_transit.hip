@@ -46,7 +46,7 @@ __global__ void k_ntot(DensityDev m, int32_t sc, const double* __restrict__ x, i
 // Molecular per-sample data (gasProperties.py:925-936): for every molecular slot m and sample
 // (o, ip, x): P = (n_tot * k_B) * T clipped below at 1e-4, its bracket on the table's P axis (-1 when
 // outside: RegularGridInterpolator's fill, 10^fill - offset = 0), the P weight, and n_abs = n_tot chi.
-// molcol[m][o][ip] = sum_x n_abs dx over in-table samples (the chord's bound / sigma_max).
+// molcol[m][o][ip] = sum_x n_abs dx over in-table samples (the chord's bound / sigma_max; NaN with a NaN sample).
 __global__ void k_mol_prep(const MolSlotDev* __restrict__ ms, int32_t n_mol, const double* __restrict__ ntot,
                            int32_t n_x, int32_t n_pr, int32_t n_orb, double delta_x, double4* __restrict__ msmp,
                            int32_t* __restrict__ mnin, double* __restrict__ molcol) {
@@ -70,7 +70,14 @@ __global__ void k_mol_prep(const MolSlotDev* __restrict__ ms, int32_t n_mol, con
       int64_t i;
       double t;
       const bool in = rgi_bracket(d.P, d.n_p, P, &i, &t);
-      if (!in) continue;
+      // a NaN sample is kept as an entry of interval 0 with n_abs = NaN: the reference's interpolator returns NaN for a
+      // NaN coordinate and n_abs is NaN as well, so the chord's tau is NaN at every wavelength, in-table or not (NaN
+      // times the out-of-table mask's 0 stays NaN); molcol, and with it the chord's bound, is NaN: the chord stays active
+      if (!in) {
+        if (n == n) continue;
+        i = 0;
+        t = 0.0;
+      }
       const double na = n * d.chi;
       msmp[k0 + nin] = make_double4(t, na, (double)i, 0.0);
       ++nin;
