@@ -360,6 +360,63 @@ int32_t prom_spectrum_vmap(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const do
  * prom_transit_set, prom_observe_set or prom_vmap_set. */
 int32_t prom_vmap_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
 
+/* ---- exposures on the device -----------------------------------------------------------------
+ * Data at any phase, smeared over its duration.  An exposure is a weighted sum of a few taps; a tap is a row of R
+ * read in its own frame: the row's model spectrum M at a factor F.  Interpolation between neighbouring model phases
+ * is two taps, the average over an exposure's duration n_sub such pairs, trial velocities put a trial axis on the
+ * factors (prometheus_amd/observation.py, exposure_taps).  All float64; the roundings named here are part of the
+ * definition.
+ *
+ *   inputs               the resident observation (prom_observe_set): only its pixels lam, sig, k and its n_orb are
+ *                        used, not its own f, data and ivar; a spectrum wav[n_wav], R[n_orb][n_wav] that covers the
+ *                        whole grid (both edges NaN, as for the maps); a resident exposure table with n_exp >= 1,
+ *                        n_trial >= 1, n_tap >= 1:
+ *                          row[n_exp][n_tap]          int32, every entry in [0, n_orb)
+ *                          a[n_exp][n_tap]            finite and >= 0
+ *                          F[n_exp][n_trial][n_tap]   finite and > 0
+ *                          data[n_exp][n_pix], ivar[n_exp][n_pix]   in the device's pixel order
+ *   taps                 tap i of (e, j) is live when a[e][i] > 0.  A dead tap is skipped altogether: it is never
+ *                        read and adds nothing, a NaN in its row does not matter (the padding rule).  A live tap's
+ *                        pixel has L = fl(lam[p] F[e][j][i]), S = fl(sig[p] F[e][j][i]), c = fl(k S); the support,
+ *                        the weights g and q, num_i, den_i and M_i = num_i / den_i are those of the observation's
+ *                        definition on row row[e][i], added in the order the velocity map uses for the same pixel
+ *                        and factor
+ *   exposure model       M_e[p] starts from the first live tap's fl(a_i M_i); each later live tap's fl(a_i M_i) is
+ *                        added in ascending i.  It is not renormalised: the host makes the weights sum to 1
+ *   used pixels          (e, j, p) is used when ivar[e][p] is finite and > 0, data[e][p] is finite, at least one tap
+ *                        is live and every live tap has den_i > 0
+ *   moments              the seven moments and n_used of the velocity map, formed with M_e, data[e] and ivar[e];
+ *                        with no used pixel zeros; a used pixel with NaN M_e makes m1, m3, m4 and m6 NaN and leaves
+ *                        the rest alone
+ *   models on request    model[e][j][p] = M_e; NaN where the pixel has no live tap or a live tap has den_i = 0.  Data
+ *                        and ivar play no part in it
+ *   independence         the numbers of (e, j) depend only on the spectrum, the pixels, exposure e's live taps in
+ *                        order (their rows, weights and F[e][j][.]), data[e] and ivar[e]: not on n_exp, n_trial,
+ *                        n_tap or the position of e or j, other exposures or trials, dead taps wherever they stand,
+ *                        whether a support was read from LDS or from global memory, or the launcher's batches.  Two
+ *                        calls agree bit for bit; there are no floating-point atomics
+ *   degenerate case      n_exp = n_orb, one tap, row[e][0] = e and a = 1: the eight numbers are prom_spectrum_vmap's
+ *                        for the table F[e][j], bit for bit (fl(1 M) = M, and the first live tap starts the sum) */
+
+/* Make the exposure table resident.  PROM_E_ARG when a shape or value rule above is broken (n_exp <= 65535,
+ * n_tap <= 65536, n_exp n_trial n_tap <= 2^28); PROM_E_STATE without a resident observation.  A later
+ * prom_observe_set, or a prom_transit_set with another n_orb, drops the table (the expose calls then fail with
+ * PROM_E_STATE). */
+int32_t prom_expose_set(prom_ctx* ctx, int32_t n_exp, int32_t n_trial, int32_t n_tap, const int32_t* row,
+                        const double* a, const double* F, const double* data, const double* ivar);
+/* The exposures over the last run's R on its stream: mom_out [n_exp][n_trial][7], n_used_out [n_exp][n_trial],
+ * model_out [n_exp][n_trial][n_pix].  Each may be NULL and is then neither formed nor copied.  The partial records
+ * take n_exp * n_trial * ceil(ceil(n_pix / 32) / 16) * 64 bytes of device scratch under the map's cap
+ * (PROM_VMAP_SCRATCH_MB): a larger table runs in batches of whole groups of 8 trials, with the same results bit
+ * for bit. */
+int32_t prom_transit_expose(prom_ctx* ctx, double* mom_out, int64_t* n_used_out, double* model_out);
+/* The same for a spectrum the caller supplies (the checks of prom_spectrum_vmap; n_orb is the observation's). */
+int32_t prom_spectrum_expose(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                             double* mom_out, int64_t* n_used_out, double* model_out);
+/* Measurement aid (tools/expose_bench.py), not for callers: mean device duration in milliseconds of k_expose
+ * (moments only) over n_runs repetitions of the last expose call, as prom_vmap_kernel_ms. */
+int32_t prom_expose_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
+
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop
  * events on its own dispatch packet (groups of kernels: the first start to the last stop).  ms_out[k] is

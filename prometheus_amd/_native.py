@@ -128,6 +128,11 @@ SIGNATURES = {
     "prom_transit_vmap": (C.c_int32, [C.c_void_p, _dp, C.POINTER(C.c_int64)]),
     "prom_spectrum_vmap": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
     "prom_vmap_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
+    "prom_expose_set": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, _dp,
+                                    _dp]),
+    "prom_transit_expose": (C.c_int32, [C.c_void_p, _dp, C.POINTER(C.c_int64), _dp]),
+    "prom_spectrum_expose": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int64), _dp]),
+    "prom_expose_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -249,6 +254,8 @@ class Device:
         self._obs_key = None
         self._vm_shape = None
         self._vm_key = None
+        self._ex_shape = None
+        self._ex_key = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -377,6 +384,7 @@ class Device:
         if self._obs_shape is not None and self._obs_shape[0] != prob.struct.n_orb:
             self._obs_shape = self._obs_key = None   # the library dropped the observation
             self._vm_shape = self._vm_key = None     # ... and the trial table with it
+            self._ex_shape = self._ex_key = None     # ... and the exposure table
         self._n_atoms = prob.n_atoms
         self._n_pr = prob.struct.n_pr
 
@@ -454,6 +462,7 @@ class Device:
                 raise ValueError("observe_set: data and ivar must be [n_orb][n_pix]")
         self._obs_shape = self._obs_key = None
         self._vm_shape = self._vm_key = None   # the library drops the trial table with the observation it was set for
+        self._ex_shape = self._ex_key = None   # ... and the exposure table
         self._check(self.lib.prom_observe_set(self.h, n_pix, _d(lam), _d(sig), float(k), n_orb,
                                               _d(f) if f is not None else None,
                                               _d(data) if data is not None else None,
@@ -552,6 +561,68 @@ class Device:
         """prom_vmap_kernel_ms: mean device duration [ms] of k_vmap for the last map call's launch."""
         ms = C.c_double(0.0)
         self._check(self.lib.prom_vmap_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_vmap_kernel_ms")
+        return float(ms.value)
+
+    # ---- exposures (prom_hip.h "exposures on the device") --------------------------------------
+    def expose_set(self, rows, weights, factors, data, ivar, key=None) -> None:
+        """prom_expose_set: the exposure table for the resident observation's pixels: rows [n_exp][n_tap] (int, in
+        [0, n_orb)), weights [n_exp][n_tap] (finite, >= 0), factors [n_exp][n_trial][n_tap] (finite, > 0), data and
+        ivar [n_exp][n_pix] in the device's pixel order.  ``key``: any value the caller keeps in ``expose_key`` to
+        skip a later upload of the same table."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        a, F, data, ivar = _f64(weights), _f64(factors), _f64(data), _f64(ivar)
+        if rows.ndim != 2 or a.shape != rows.shape:
+            raise ValueError("expose_set: rows and weights must be [n_exp][n_tap]")
+        n_exp, n_tap = rows.shape
+        if F.ndim != 3 or F.shape[0] != n_exp or F.shape[2] != n_tap:
+            raise ValueError("expose_set: factors must be [n_exp][n_trial][n_tap]")
+        n_pix = (self._obs_shape or (0, 0))[1]
+        if data.shape != (n_exp, n_pix) or ivar.shape != (n_exp, n_pix):
+            raise ValueError("expose_set: data and ivar must be [n_exp][n_pix] of the resident observation")
+        self._ex_shape = self._ex_key = None
+        self._check(self.lib.prom_expose_set(self.h, n_exp, F.shape[1], n_tap, rows.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             _d(a), _d(F), _d(data), _d(ivar)), "prom_expose_set")
+        self._ex_shape = (n_exp, F.shape[1], n_pix)
+        self._ex_key = key
+
+    @property
+    def expose_key(self):
+        """The ``key`` of the exposure table resident on the context (None: none, or set without a key)."""
+        return self._ex_key
+
+    def _expose_outputs(self, moments: bool, model: bool):
+        n_exp, n_trial, n_pix = self._ex_shape or (0, 0, 0)
+        mom = np.zeros((n_exp, n_trial, 7)) if moments else None
+        nu = np.zeros((n_exp, n_trial), dtype=np.int64) if moments else None
+        mod = None
+        if model:
+            # NaN: what a table without pixels leaves (the library writes nothing then)
+            mod = np.full((n_exp, n_trial, n_pix), np.nan)
+        ptr = (_d(mom) if moments else None, nu.ctypes.data_as(C.POINTER(C.c_int64)) if moments else None,
+               _d(mod) if model else None)
+        return (mom, nu, mod), ptr
+
+    def transit_expose(self, moments: bool = True, model: bool = False):
+        """prom_transit_expose over the last run's R: (moments [n_exp][n_trial][7], n_used [n_exp][n_trial], model
+        [n_exp][n_trial][n_pix]), None for what was not asked."""
+        out, ptr = self._expose_outputs(moments, model)
+        self._check(self.lib.prom_transit_expose(self.h, *ptr), "prom_transit_expose")
+        return out
+
+    def spectrum_expose(self, wav, R, moments: bool = True, model: bool = False):
+        """prom_spectrum_expose of R[n_orb][n_wav] on the ascending grid wav: (moments, n_used, model)."""
+        wav, R = _f64(wav), _f64(R)
+        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
+            raise ValueError("spectrum_expose: R must be [n_orb][n_wav]")
+        out, ptr = self._expose_outputs(moments, model)
+        self._check(self.lib.prom_spectrum_expose(self.h, R.shape[0], len(wav), _d(wav), _d(R), *ptr),
+                    "prom_spectrum_expose")
+        return out
+
+    def expose_kernel_ms(self, n_runs: int = 20) -> float:
+        """prom_expose_kernel_ms: mean device duration [ms] of k_expose for the last expose call's launch."""
+        ms = C.c_double(0.0)
+        self._check(self.lib.prom_expose_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_expose_kernel_ms")
         return float(ms.value)
 
     # ---- stellar disk -----------------------------------------------------------------------

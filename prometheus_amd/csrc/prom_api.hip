@@ -602,6 +602,8 @@ int32_t prom_transit_set(prom_ctx* ctx, const prom_transit_problem* pb) {
     ctx->obs.last_wav = ctx->obs.last_R = nullptr;   // (this set may move the buffers the last observe call read)
     if (ctx->vm.set && ctx->vm.n_orb != pb->n_orb) ctx->vm.set = false;      // ... and the trial table's with them
     ctx->vm.last_wav = ctx->vm.last_R = nullptr;
+    if (ctx->ex.set && ctx->ex.n_orb != pb->n_orb) ctx->ex.set = false;      // ... and the exposure table's rows
+    ctx->ex.last_wav = ctx->ex.last_R = nullptr;
     tr.n_x = pb->n_x;
     tr.n_sc = pb->n_scenarios;
     tr.n_moons = pb->n_moons;
@@ -1820,6 +1822,8 @@ int32_t prom_observe_set(prom_ctx* ctx, int32_t n_pix, const double* lam, const 
     ob.set = false;
     ctx->vm.set = false;   // a trial table belongs to the observation it was set for
     ctx->vm.last_wav = ctx->vm.last_R = nullptr;
+    ctx->ex.set = false;   // ... and so does an exposure table (its data are in the observation's pixels)
+    ctx->ex.last_wav = ctx->ex.last_R = nullptr;
     PROM_REQUIRE(n_pix >= 0 && n_orb >= 1 && n_orb <= 65535 && (n_pix == 0 || (lam && sig)),
                  "prom_observe_set: bad shape");
     PROM_REQUIRE(k > 0.0 && obs_finite(k), "prom_observe_set: the truncation k must be positive");
@@ -2077,6 +2081,158 @@ int32_t prom_vmap_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
     double sum = 0.0;
     for (int32_t r = 0; r < n_runs; ++r) {
       vmap_launch(ctx, st, vm.last_wav, vm.last_R, vm.last_n_wav, ctx->ev[0], ctx->ev[1]);
+      PROM_HIP(hipStreamSynchronize(st));
+      float ms = 0.0f;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      sum += ms;
+    }
+    *ms_out = scale * sum / n_runs;
+  });
+}
+
+// ------------------------------------------------------------------------------ exposures
+int32_t prom_expose_set(prom_ctx* ctx, int32_t n_exp, int32_t n_trial, int32_t n_tap, const int32_t* row,
+                        const double* a, const double* F, const double* data, const double* ivar) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    const prom::ObsDev& ob = ctx->obs;
+    ex.set = false;
+    ex.last_wav = ex.last_R = nullptr;
+    PROM_REQUIRE(n_exp >= 1 && n_exp <= 65535 && n_trial >= 1 && n_trial <= (1 << 24) && n_tap >= 1 &&
+                     n_tap <= (1 << 16) && row && a && F,
+                 "prom_expose_set: bad shape");
+    if (!ob.set) throw Error(PROM_E_STATE, "prom_expose_set: no observation on the context (prom_observe_set)");
+    PROM_REQUIRE(ob.n_pix == 0 || (data && ivar), "prom_expose_set: data and ivar missing");
+    const int64_t nt = (int64_t)n_exp * n_tap, nf = nt * n_trial, nd = (int64_t)n_exp * ob.n_pix;
+    PROM_REQUIRE(nf <= ((int64_t)1 << 28), "prom_expose_set: table too large");
+    for (int64_t i = 0; i < nt; ++i) {
+      PROM_REQUIRE(row[i] >= 0 && row[i] < ob.n_orb, "prom_expose_set: a tap's row lies outside [0, n_orb)");
+      PROM_REQUIRE(a[i] >= 0.0 && obs_finite(a[i]), "prom_expose_set: tap weights must be finite and >= 0");
+    }
+    for (int64_t i = 0; i < nf; ++i)
+      PROM_REQUIRE(F[i] > 0.0 && obs_finite(F[i]), "prom_expose_set: factors must be finite and positive");
+    const hipStream_t st = ctx->stream;
+    upload(ex.row, row, nt, st);
+    upload(ex.a, a, nt, st);
+    upload(ex.F, F, nf, st);
+    upload(ex.data, data, nd, st);
+    upload(ex.ivar, ivar, nd, st);
+    ex.mom.ensure(sizeof(double) * 7 * (size_t)n_exp * n_trial);
+    ex.n_used.ensure(sizeof(int64_t) * (size_t)n_exp * n_trial);
+    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
+    ex.n_orb = ob.n_orb;
+    ex.n_exp = n_exp;
+    ex.n_trial = n_trial;
+    ex.n_tap = n_tap;
+    ex.set = true;
+  });
+}
+
+// one pass over the table in batches of whole trial groups (ev: events around the k_expose launch of the first batch)
+static void expose_launch(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int32_t n_wav,
+                          bool want_mom, double* model, hipEvent_t ev0, hipEvent_t ev1) {
+  prom::ExDev& ex = ctx->ex;
+  const prom::ObsDev& ob = ctx->obs;
+  const int32_t n_chunks = prom::vm_chunks(ob.n_pix), n_groups = prom::vm_groups(ex.n_trial);
+  const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, n_chunks, n_groups);
+  const int32_t nb_max = std::min(bg * prom::kVmTrials, ex.n_trial);
+  ex.part.ensure(sizeof(double) * (size_t)prom::vm_part_doubles(ex.n_exp, nb_max, n_chunks));
+  static const bool debug = std::getenv("PROM_DEBUG") != nullptr;
+  if (debug)
+    std::fprintf(stderr, "prom: exposures: %d trials in %d groups, %d batches of up to %d groups, %d chunks\n",
+                 ex.n_trial, n_groups, (n_groups + bg - 1) / bg, bg, n_chunks);
+  for (int32_t g = 0; g < n_groups; g += bg) {
+    const int32_t j_first = prom::vm_group_first(g), nb = std::min(nb_max, ex.n_trial - j_first);
+    prom::launch_expose(st, wav, ex.q.as<double>(), R, n_wav, ob.lam.as<double>(), ob.sig.as<double>(), ob.k,
+                        ex.row.as<int32_t>(), ex.a.as<double>(), ex.F.as<double>(), ex.data.as<double>(),
+                        ex.ivar.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, ex.n_tap, j_first, nb,
+                        ex.part.as<double>(), model, g == 0 ? ev0 : nullptr, g == 0 ? ev1 : nullptr);
+    if (want_mom)
+      prom::launch_vmap_reduce(st, ex.part.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, j_first, nb,
+                               ex.mom.as<double>(), ex.n_used.as<int64_t>());
+  }
+}
+
+// the shared tail of the two expose calls: q of the whole grid, the batches and the copies back, on stream st
+static void expose_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, double* mom_out,
+                      int64_t* n_used_out, double* model_out) {
+  prom::ExDev& ex = ctx->ex;
+  const int64_t n = (int64_t)ex.n_exp * ex.n_trial;
+  if (ctx->obs.n_pix == 0) {   // no pixel: every moment 0 and no model value
+    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
+    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
+    return;
+  }
+  if (!mom_out && !n_used_out && !model_out) return;
+  const double nan = std::nan("");
+  const int64_t nm = n * ctx->obs.n_pix;
+  ex.q.ensure(sizeof(double) * (size_t)n_wav);
+  if (model_out) ex.model.ensure(sizeof(double) * (size_t)nm);
+  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
+  expose_launch(ctx, st, wav, R, (int32_t)n_wav, mom_out || n_used_out, model_out ? ex.model.as<double>() : nullptr,
+                nullptr, nullptr);
+  ex.last_wav = wav;
+  ex.last_R = R;
+  ex.last_n_wav = (int32_t)n_wav;
+  if (mom_out) download(mom_out, ex.mom, 7 * n, st);
+  if (n_used_out) download(n_used_out, ex.n_used, n, st);
+  if (model_out) download(model_out, ex.model, nm, st);
+  PROM_HIP(hipStreamSynchronize(st));
+}
+
+static void expose_check(prom_ctx* ctx, const char* who) {
+  if (!ctx->ex.set || !ctx->obs.set || ctx->obs.n_orb != ctx->ex.n_orb)
+    throw Error(PROM_E_STATE, std::string(who) + ": no exposure table on the context (prom_expose_set; a later "
+                                                 "prom_observe_set or a prom_transit_set with another n_orb drops it)");
+}
+
+int32_t prom_transit_expose(prom_ctx* ctx, double* mom_out, int64_t* n_used_out, double* model_out) {
+  return guarded(ctx, [&] {
+    prom::TransitDev& tr = ctx->tr;
+    expose_check(ctx, "prom_transit_expose");
+    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose: no completed run");
+    if (ctx->ex.n_orb != tr.n_orb)
+      throw Error(PROM_E_STATE, "prom_transit_expose: the exposure table has another n_orb");
+    // the last run's stream orders the exposures after it
+    expose_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, mom_out,
+              n_used_out, model_out);
+  });
+}
+
+int32_t prom_spectrum_expose(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                             double* mom_out, int64_t* n_used_out, double* model_out) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    expose_check(ctx, "prom_spectrum_expose");
+    PROM_REQUIRE(n_orb == ex.n_orb, "prom_spectrum_expose: n_orb differs from the observation's");
+    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_expose: bad spectrum");
+    for (int64_t w = 0; w < n_wav; ++w)
+      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
+                   "prom_spectrum_expose: wavelengths must be finite and ascending");
+    const hipStream_t st = ctx->stream;
+    ex.last_wav = ex.last_R = nullptr;   // (the uploads may move the buffers the last call read)
+    upload(ex.wav, wav, n_wav, st);
+    upload(ex.R, R, (int64_t)n_orb * n_wav, st);
+    expose_on(ctx, st, ex.wav.as<double>(), ex.R.as<double>(), n_wav, mom_out, n_used_out, model_out);
+  });
+}
+
+int32_t prom_expose_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_expose_kernel_ms: bad arguments");
+    if (!ex.set || !ctx->obs.set || !ex.last_wav || ctx->obs.n_pix == 0)
+      throw Error(PROM_E_STATE, "prom_expose_kernel_ms: no expose call to repeat");
+    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
+    const hipStream_t st = ctx->stream;
+    // k_expose of the first batch (the whole table when it fits the scratch cap), scaled to the table by trial count;
+    // moments only, no model store
+    const int32_t n_groups = prom::vm_groups(ex.n_trial);
+    const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, prom::vm_chunks(ctx->obs.n_pix), n_groups);
+    const double scale = (double)ex.n_trial / (double)std::min(bg * prom::kVmTrials, ex.n_trial);
+    double sum = 0.0;
+    for (int32_t r = 0; r < n_runs; ++r) {
+      expose_launch(ctx, st, ex.last_wav, ex.last_R, ex.last_n_wav, true, nullptr, ctx->ev[0], ctx->ev[1]);
       PROM_HIP(hipStreamSynchronize(st));
       float ms = 0.0f;
       PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));

@@ -443,6 +443,20 @@ struct VmDev {
   int32_t last_n_wav = 0;
 };
 
+// The exposure table resident on a context (prom_expose_set) and the work buffers of the expose calls.
+struct ExDev {
+  bool set = false;
+  int32_t n_orb = 0, n_exp = 0, n_trial = 0, n_tap = 0;
+  DevBuf row, a, F, data, ivar;           // [n_exp][n_tap] int32, [n_exp][n_tap], [n_exp][n_trial][n_tap], [n_exp][n_pix] x 2
+  DevBuf q, part, mom, n_used, model;     // [n_wav], the batch's partial records, [n_exp][n_trial][7], [n_exp][n_trial],
+                                          // [n_exp][n_trial][n_pix] (on request)
+  DevBuf wav, R;                          // prom_spectrum_expose's copies of the caller's spectrum
+  // the last call's spectrum, for prom_expose_kernel_ms to repeat (null: none yet)
+  const double* last_wav = nullptr;
+  const double* last_R = nullptr;
+  int32_t last_n_wav = 0;
+};
+
 }  // namespace prom
 
 struct prom_ctx {
@@ -457,6 +471,7 @@ struct prom_ctx {
   prom::TransitDev tr;
   prom::ObsDev obs;
   prom::VmDev vm;
+  prom::ExDev ex;
   int64_t vmap_scratch_bytes = (int64_t)256 << 20;   // PROM_VMAP_SCRATCH_MB: cap of k_vmap's partial records
   prom::DevBuf scratch[6];
   bool timing = false;
@@ -558,6 +573,13 @@ void launch_vmap(hipStream_t s, const double* wav, const double* q, const double
                  hipEvent_t ev1);
 void launch_vmap_reduce(hipStream_t s, const double* part, int32_t n_pix, int32_t n_orb, int32_t n_trial,
                         int32_t j_first, int32_t nb, double* mom, int64_t* n_used);
+// exposures (prom_expose.hip): the moments of trials [j_first, j_first + nb) of every exposure into the batch's partial
+// records part[n_exp][nb][chunks][8] (launch_vmap_reduce adds them, with n_exp for n_orb) and, where model is not
+// null, model[n_exp][n_trial][n_pix]
+void launch_expose(hipStream_t s, const double* wav, const double* q, const double* R, int32_t n_wav, const double* lam,
+                   const double* sig, double k, const int32_t* row, const double* wgt, const double* F,
+                   const double* data, const double* ivar, int32_t n_pix, int32_t n_exp, int32_t n_trial, int32_t n_tap,
+                   int32_t j_first, int32_t nb, double* part, double* model, hipEvent_t ev0, hipEvent_t ev1);
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

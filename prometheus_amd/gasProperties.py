@@ -648,6 +648,31 @@ class _VmapJob:
         self.moments, self.n_used = part
 
 
+class _ExposeJob:
+    """One Transit.expose call inside _integrate: the pixels and the exposure table go to the device once each while
+    their content keys are unchanged, then the exposures run over the (one) chunk's R."""
+
+    def __init__(self, exposures, n_orb, want_model):
+        self.ex = exposures
+        self.obs = _ObserveJob(exposures.pixels(n_orb), False)
+        self.want_model = want_model
+        self.whole = False
+        self.moments = self.n_used = self.model = None
+
+    def upload(self, dev) -> None:
+        self.obs.upload(dev)
+        if dev.expose_key != self.ex.key:
+            dev.expose_set(self.ex.rows, self.ex.weights, self.ex.factors, self.ex.data, self.ex.ivar, key=self.ex.key)
+
+    def run(self, dev, wavelength, a: int, b: int):
+        if not self.whole:   # (expose refuses such a run before it starts)
+            raise RuntimeError("expose: the run was split into wavelength shards or chunks")
+        return dev.transit_expose(moments=True, model=self.want_model)
+
+    def add(self, part) -> None:
+        self.moments, self.n_used, self.model = part
+
+
 _STAR_TABLES: "weakref.WeakKeyDictionary" = None
 
 
@@ -914,6 +939,41 @@ class Transit:
         job = _VmapJob(observation, F)
         self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
         return obs.VelocityMap(job.moments, job.n_used, F)
+
+    def expose(self, exposures, return_model: bool = False, devices: Optional[Sequence[int]] = None,
+               max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0):
+        """Run the transit and compare it on the device with exposures taken at any phase and smeared over their
+        duration: ``exposures`` is an observation.Exposures (rows, weights and factors from
+        observation.exposure_taps, data and err per exposure).  R stays in device memory; per (exposure, trial) the
+        seven moments of the exposure's model against its data come back as an observation.VelocityMap whose first
+        axis counts exposures and whose ``factors`` is the exposures' table; with ``return_model`` its ``model``
+        holds the exposures' model spectra [n_exp][n_trial][n_pix] in the caller's pixel order.  The pixels and the
+        table are uploaded once each while their content is unchanged.
+
+        As for velocity_map the run must be one wavelength shard on one device in one chunk: otherwise ValueError,
+        before anything is uploaded or run; ValueError too when a tap's row is not one of the transit's phases."""
+        from . import observation as obs
+        if not isinstance(exposures, obs.Exposures):
+            raise TypeError("expose: exposures must be an observation.Exposures")
+        n_orb = len(self.spatialGrid.constructOrbphaseAxis())
+        if int(exposures.rows.max()) >= n_orb or int(exposures.rows.min()) < 0:
+            raise ValueError("expose: a tap reads row %d, the transit has %d phases"
+                             % (int(exposures.rows.max()), n_orb))
+        if not hasattr(self, "wavelength"):
+            self.addWavelength()
+        devices = [0] if devices is None else list(devices)
+        max_memory_gb = 2.0 if max_memory_gb is None else max_memory_gb
+        n_wav, chunk = len(self.wavelength), self._wavelength_chunk(max_memory_gb, n_orb)
+        if len(devices) != 1 or n_wav > chunk:
+            raise ValueError(
+                "expose: the run would be split into %d wavelength shard(s) and chunks of %d wavelengths (the grid "
+                "has %d); the moments are not additive over wavelength partials (a tap's model M = num / den needs "
+                "the sums of the whole grid before it meets the data).  Give one device and raise max_memory_gb "
+                "until the grid fits one chunk." % (len(devices), chunk, n_wav))
+        job = _ExposeJob(exposures, n_orb, return_model)
+        self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
+        model = exposures.instrument.unsort(job.model) if return_model else None
+        return obs.VelocityMap(job.moments, job.n_used, exposures.factors, model=model)
 
     def _wavelength_chunk(self, max_memory_gb, n_orb: int) -> int:
         """Wavelengths per device step under ``max_memory_gb``."""

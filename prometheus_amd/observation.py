@@ -94,6 +94,67 @@ class Observation:
         self.key = (self.n_orb, instrument.truncate, self.f is None, self.data is None) + _content_fingerprint(*arrays)
 
 
+class Exposures:
+    """Data at any phase, smeared over its duration: what stays resident on the device between Transit.expose calls.
+    An exposure is a weighted sum of taps; a tap is a row of the model's R read at a factor (include/prom_hip.h,
+    "exposures on the device").  ``rows`` and ``weights`` are [n_exp][n_tap] (rows: indices into the model's phase
+    axis; a tap of weight 0 is padding and is skipped), ``factors`` [n_exp][n_trial][n_tap], or [n_exp][n_tap] for one
+    trial (exposure_taps makes all three), ``data`` and its standard error ``err`` [n_exp][n_pix] in the caller's
+    pixel order, or anything that broadcasts to it (a pixel with non-finite data or err, or err <= 0, is masked).
+    Sorting, the inverse variances and the content key that lets a device skip the upload are computed once here.
+    The arrays are copied.  ValueError for a bad shape or value; that the rows lie inside the transit's phases is
+    checked by Transit.expose."""
+
+    def __init__(self, instrument: Instrument, rows, weights, factors, data, err):
+        from .gasProperties import _content_fingerprint
+        self.instrument = instrument
+        r = np.asarray(rows)
+        if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] < 1:
+            raise ValueError("Exposures: rows must be [n_exp][n_tap] with n_exp, n_tap >= 1")
+        if not (np.issubdtype(r.dtype, np.integer) or (np.issubdtype(r.dtype, np.floating) and np.all(r == np.rint(r)))):
+            raise ValueError("Exposures: rows must be integers")
+        if np.any(r < 0) or np.any(r > 65534):
+            raise ValueError("Exposures: rows must lie in [0, n_orb)")
+        self.rows = np.ascontiguousarray(r, dtype=np.int32)
+        self.n_exp, self.n_tap = self.rows.shape
+        a = np.array(weights, dtype=np.float64)
+        if a.shape != self.rows.shape:
+            raise ValueError("Exposures: weights must be [n_exp][n_tap] like rows")
+        if not (np.all(np.isfinite(a)) and np.all(a >= 0)):
+            raise ValueError("Exposures: weights must be finite and >= 0")
+        self.weights = np.ascontiguousarray(a)
+        F = np.array(factors, dtype=np.float64)
+        if F.ndim == 2:
+            F = F[:, None, :]
+        if F.ndim != 3 or F.shape[0] != self.n_exp or F.shape[2] != self.n_tap or F.shape[1] < 1:
+            raise ValueError("Exposures: factors must be [n_exp][n_trial][n_tap] (or [n_exp][n_tap] for one trial)")
+        if not (np.all(np.isfinite(F)) and np.all(F > 0)):
+            raise ValueError("Exposures: factors must be finite and positive")
+        self.factors = np.ascontiguousarray(F)
+        self.n_trial = F.shape[1]
+        if data is None or err is None:
+            raise ValueError("Exposures: data and err are needed")
+        shape = (self.n_exp, instrument.n_pix)
+        try:
+            d = np.broadcast_to(np.asarray(data, dtype=np.float64), shape)
+            e = np.broadcast_to(np.asarray(err, dtype=np.float64), shape)
+        except ValueError:
+            raise ValueError("Exposures: data and err must be [n_exp][n_pix] = [%d][%d]" % shape) from None
+        self.data = instrument.sort(d)
+        e = instrument.sort(e)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.ivar = np.where(np.isfinite(e) & (e > 0), 1.0 / (e * e), 0.0)
+        self.key = ("exposures", instrument.truncate) + _content_fingerprint(
+            instrument.lam, instrument.sig, self.rows, self.weights, self.factors, self.data, self.ivar)
+        self._pixels = {}
+
+    def pixels(self, n_orb: int) -> "Observation":
+        """The Observation that carries only the pixels, for a model of n_orb phases (made once per n_orb)."""
+        if n_orb not in self._pixels:
+            self._pixels[n_orb] = Observation(self.instrument, n_orb)
+        return self._pixels[n_orb]
+
+
 def model_spectrum(num, den) -> np.ndarray:
     """M = num / den; NaN where den == 0 (no model coverage)."""
     num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
@@ -155,6 +216,66 @@ def kp_vsys_factors(orbphase, Kp, Vsys) -> np.ndarray:
     return np.ascontiguousarray(const.calculateDopplerShift(v).reshape(len(orb), len(kp) * len(vs)))
 
 
+def exposure_taps(orbphase, base, mid, width, n_sub: int = 1, Kp=None, Vsys=None):
+    """(rows [n_exp][2 n_sub], weights [n_exp][2 n_sub], factors [n_exp][n_trial][2 n_sub]) of exposures centred at the
+    orbital phases ``mid`` [n_exp] that last ``width`` [n_exp] (>= 0), both in radians like ``orbphase``, the model's
+    ascending phase axis (at least 2 entries).  ``base`` [n_orb] holds each row's own planet factor
+    (planet_frame_shifts).
+
+    An exposure is the mean of ``n_sub`` sub-samples at phi = mid + width ((s + 1/2) / n_sub - 1/2); a sub-sample is
+    interpolated linearly between the two model phases that bracket it: with r the bracket's lower row and
+    t = (phi - orbphase[r]) / (orbphase[r + 1] - orbphase[r]) the taps are (r, (1 - t) / n_sub) and
+    (r + 1, t / n_sub).  A sub-sample outside the axis raises ValueError: there is no extrapolation.
+
+    factors[e][j][tap] = base[row] / calculateDopplerShift(-Kp_j sin(phi) + Vsys_j) over a (Kp, Vsys) grid [cm/s],
+    Kp-major as in kp_vsys_factors.  With ``Kp`` and ``Vsys`` both None there is one trial, whose denominator is
+    ``base`` interpolated linearly to phi between the bracket's rows (with the same t).
+
+    The pixels are in the frame the model is computed in.  The factor moves the planet's lines from the row's velocity
+    to the sub-sample's; features that do not move with the planet, such as a stellar spectrum with centre-to-limb
+    variation or the Rossiter-McLaughlin effect, are displaced by the same amount.  This is the approximation of
+    interpolating between phases."""
+    from . import constants as const
+    orb = np.asarray(orbphase, dtype=np.float64).reshape(-1)
+    n_orb = len(orb)
+    if n_orb < 2 or not np.all(np.isfinite(orb)) or not np.all(np.diff(orb) > 0):
+        raise ValueError("exposure_taps: orbphase must be ascending with at least 2 entries")
+    b = np.asarray(base, dtype=np.float64).reshape(-1)
+    if b.shape != (n_orb,):
+        raise ValueError("exposure_taps: base must have one factor per orbital phase")
+    mid = np.asarray(mid, dtype=np.float64).reshape(-1)
+    wid = np.asarray(width, dtype=np.float64).reshape(-1)
+    if wid.shape != mid.shape or len(mid) < 1:
+        raise ValueError("exposure_taps: mid and width must be [n_exp] with n_exp >= 1")
+    if not (np.all(np.isfinite(mid)) and np.all(np.isfinite(wid)) and np.all(wid >= 0)):
+        raise ValueError("exposure_taps: mid must be finite and width finite and >= 0")
+    n_sub = int(n_sub)
+    if n_sub < 1:
+        raise ValueError("exposure_taps: n_sub must be >= 1")
+    if (Kp is None) != (Vsys is None):
+        raise ValueError("exposure_taps: Kp and Vsys come together")
+    phi = mid[:, None] + wid[:, None] * ((np.arange(n_sub) + 0.5) / n_sub - 0.5)[None, :]   # [n_exp][n_sub]
+    if np.any(phi < orb[0]) or np.any(phi > orb[-1]):
+        raise ValueError("exposure_taps: a sub-sample lies outside the model's phases [%r, %r] (no extrapolation)"
+                         % (orb[0], orb[-1]))
+    r = np.minimum(np.searchsorted(orb, phi, "right") - 1, n_orb - 2)
+    t = (phi - orb[r]) / (orb[r + 1] - orb[r])
+    n_exp = len(mid)
+    rows = np.empty((n_exp, 2 * n_sub), dtype=np.int32)
+    rows[:, 0::2], rows[:, 1::2] = r, r + 1
+    weights = np.empty((n_exp, 2 * n_sub))
+    weights[:, 0::2], weights[:, 1::2] = (1.0 - t) / n_sub, t / n_sub
+    if Kp is None:
+        den = ((1.0 - t) * b[r] + t * b[r + 1])[:, None, :]                                  # [n_exp][1][n_sub]
+    else:
+        kp = np.asarray(Kp, dtype=np.float64).reshape(-1)
+        vs = np.asarray(Vsys, dtype=np.float64).reshape(-1)
+        v = (-np.sin(phi))[:, None, None, :] * kp[None, :, None, None] + vs[None, None, :, None]
+        den = const.calculateDopplerShift(v).reshape(n_exp, len(kp) * len(vs), n_sub)
+    factors = b[rows][:, None, :] / np.repeat(den, 2, axis=2)
+    return rows, weights, np.ascontiguousarray(factors)
+
+
 def _ratio(a, b):
     """a / b, NaN where b == 0."""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
@@ -167,11 +288,14 @@ class VelocityMap:
     every trial frame against the data (include/prom_hip.h, "velocity maps on the device"; m0 = sum iv,
     m1 = sum iv M, m2 = sum iv d, m3 = sum iv M^2, m4 = sum iv M d, m5 = sum iv d^2, m6 = sum iv (M - d)^2 over the
     used pixels) and the table ``factors`` they belong to.  The statistics are per (phase, trial), NaN where their
-    denominator is 0."""
+    denominator is 0.  From Transit.expose the first axis counts exposures, ``factors`` is the exposures'
+    [n_exp][n_trial][n_tap] table and ``model`` [n_exp][n_trial][n_pix] holds the exposures' model spectra in the
+    caller's pixel order when they were asked for (None otherwise, and from velocity_map)."""
 
     STATS = ("chi2", "chi2_scaled", "scale", "ccf", "loglike")
 
-    def __init__(self, moments, n_used, factors):
+    def __init__(self, moments, n_used, factors, model=None):
+        self.model = model
         self.moments = np.asarray(moments, dtype=np.float64)
         self.n_used = np.asarray(n_used, dtype=np.int64)
         self.factors = np.asarray(factors, dtype=np.float64)
