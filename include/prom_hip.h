@@ -417,6 +417,67 @@ int32_t prom_spectrum_expose(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const 
  * (moments only) over n_runs repetitions of the last expose call, as prom_vmap_kernel_ms. */
 int32_t prom_expose_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
 
+/* ---- detrended exposures on the device --------------------------------------------------------
+ * A systematics basis projected out of the exposures' model.  Data cleaned with SYSREM or PCA have lost part of the
+ * planet's signal with the tellurics, so the model goes through the same linear filter before it meets them: per
+ * pixel column p, over the exposures, m' = m - U (W_p m) (Gibson et al. 2022).  The filter couples all exposures of
+ * a pixel; the host makes U and W (prometheus_amd/observation.py, sysrem and filter_weights).  All float64; the
+ * roundings named here are part of the definition.
+ *
+ *   inputs               the resident observation and exposure table (prom_expose_set), a spectrum over the whole
+ *                        grid, and a resident filter with 1 <= n_comp <= 16:
+ *                          U[n_exp][n_comp]           finite: the basis the data were cleaned with
+ *                          W[n_comp][n_exp][n_pix]    finite, in the device's pixel order, p fastest: the basis'
+ *                                                     (inverse-variance weighted) pseudo-inverse at pixel p
+ *   unfiltered model     M[e][j][p] is prom_spectrum_expose's model_out value, bit for bit
+ *   filterable column    column (j, p) is filterable when M[e][j][p] is not NaN for every e that has
+ *                        W[k][e][p] != 0 for some k
+ *   coefficients         c_k starts at +0; in ascending e every term with W[k][e][p] != 0 adds
+ *                        fl(W[k][e][p] M[e][j][p]).  A term with W = 0 is skipped altogether and its M is never
+ *                        read into the sum (the padding rule: masked pixels carry W = 0)
+ *   filtered model       M'_e starts at M_e and takes, in ascending k, M'_e <- fl(M'_e - fl(U[e][k] c_k)): every
+ *                        product and every sum is rounded on its own, there is no fused multiply-add, and a plain
+ *                        numpy loop gives the same bits.  In a column that is not filterable every M'_e is NaN
+ *   used pixels          (e, j, p) is used when ivar[e][p] is finite and > 0, data[e][p] is finite, the column is
+ *                        filterable and M[e][j][p] is not NaN.  A NaN model value therefore always un-uses its
+ *                        pixel, whatever its cause (no coverage, or a NaN in R), and never reaches a moment.  This is
+ *                        deliberately simpler than the exposures' rule (a used pixel with NaN M_e makes moments
+ *                        NaN there): coverage is no longer known once only the model is in memory.  The kernel
+ *                        tests M'_e, which in a filterable column is NaN where M_e is; it is NaN elsewhere only
+ *                        when an infinity arose (one in R, or an overflowing product), and such a pixel is unused too
+ *   moments              the seven moments and n_used of the velocity map, formed with M'_e, data[e] and ivar[e];
+ *                        m6 directly from (M' - d); added in the map's shape (thread t of a 32-pixel tile, a
+ *                        32-lane xor butterfly per tile, tiles in order within a chunk of 16, the chunks' records
+ *                        in chunk order); with no used pixel zeros
+ *   models on request    model[e][j][p] = M'_e
+ *   independence         the numbers of (e, j) depend only on the spectrum, the pixels, the exposures' live taps,
+ *                        column j's factors F[.][j][.], the filter, data[e] and ivar[e]: not on n_trial, j's
+ *                        position, other trials or the launcher's batches.  Two calls agree bit for bit; there are
+ *                        no floating-point atomics
+ *   degenerate case      U = 0 with any finite W, and an R and table for which no M is NaN: the eight numbers and
+ *                        the model are prom_spectrum_expose's, bit for bit (fl(0 c) = 0, x - 0 = x, and the moments
+ *                        are added in the same shape) */
+
+/* Make the filter resident: U[n_exp][n_comp] and W[n_comp][n_exp][n_pix].  PROM_E_STATE without a resident exposure
+ * table; PROM_E_ARG when n_exp differs from the table's, n_comp lies outside [1, 16] or an entry is not finite.
+ * prom_expose_set, and whatever drops the exposure table, drops the filter (the detrended calls then fail with
+ * PROM_E_STATE). */
+int32_t prom_detrend_set(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, const double* U, const double* W);
+/* The detrended exposures over the last run's R on its stream: the outputs and checks of prom_transit_expose, each
+ * output may be NULL, n_pix = 0 gives zeros.  The unfiltered model of the whole table is formed first and filtered
+ * in place, so n_exp * n_trial * n_pix * 8 bytes of device memory hold it, whatever PROM_VMAP_SCRATCH_MB says (the
+ * cap still batches the moments' partial records): a table whose model does not fit fails with PROM_E_NOMEM, and the
+ * remedy is fewer trials per call. */
+int32_t prom_transit_expose_detrended(prom_ctx* ctx, double* mom_out, int64_t* n_used_out, double* model_out);
+/* The same for a spectrum the caller supplies (the checks of prom_spectrum_expose). */
+int32_t prom_spectrum_expose_detrended(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                       double* mom_out, int64_t* n_used_out, double* model_out);
+/* Measurement aid (tools/detrend_bench.py), not for callers: mean device durations in milliseconds over n_runs
+ * repetitions of the last detrended call: ms_out[0] k_detrend (the whole table), ms_out[1] k_model_moments (the first
+ * batch, scaled as prom_vmap_kernel_ms).  The filter works in place, so each repetition forms the unfiltered model
+ * again (untimed) before it.  PROM_E_STATE when there is no such call. */
+int32_t prom_detrend_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
+
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop
  * events on its own dispatch packet (groups of kernels: the first start to the last stop).  ms_out[k] is

@@ -133,6 +133,11 @@ SIGNATURES = {
     "prom_transit_expose": (C.c_int32, [C.c_void_p, _dp, C.POINTER(C.c_int64), _dp]),
     "prom_spectrum_expose": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int64), _dp]),
     "prom_expose_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
+    "prom_detrend_set": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]),
+    "prom_transit_expose_detrended": (C.c_int32, [C.c_void_p, _dp, C.POINTER(C.c_int64), _dp]),
+    "prom_spectrum_expose_detrended": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, _dp,
+                                                   C.POINTER(C.c_int64), _dp]),
+    "prom_detrend_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -256,6 +261,7 @@ class Device:
         self._vm_key = None
         self._ex_shape = None
         self._ex_key = None
+        self._dt_key = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -385,6 +391,7 @@ class Device:
             self._obs_shape = self._obs_key = None   # the library dropped the observation
             self._vm_shape = self._vm_key = None     # ... and the trial table with it
             self._ex_shape = self._ex_key = None     # ... and the exposure table
+            self._dt_key = None                      # ... with its filter
         self._n_atoms = prob.n_atoms
         self._n_pr = prob.struct.n_pr
 
@@ -463,6 +470,7 @@ class Device:
         self._obs_shape = self._obs_key = None
         self._vm_shape = self._vm_key = None   # the library drops the trial table with the observation it was set for
         self._ex_shape = self._ex_key = None   # ... and the exposure table
+        self._dt_key = None                    # ... with its filter
         self._check(self.lib.prom_observe_set(self.h, n_pix, _d(lam), _d(sig), float(k), n_orb,
                                               _d(f) if f is not None else None,
                                               _d(data) if data is not None else None,
@@ -580,6 +588,7 @@ class Device:
         if data.shape != (n_exp, n_pix) or ivar.shape != (n_exp, n_pix):
             raise ValueError("expose_set: data and ivar must be [n_exp][n_pix] of the resident observation")
         self._ex_shape = self._ex_key = None
+        self._dt_key = None   # the library drops the filter with the table it was set for
         self._check(self.lib.prom_expose_set(self.h, n_exp, F.shape[1], n_tap, rows.ctypes.data_as(C.POINTER(C.c_int32)),
                                              _d(a), _d(F), _d(data), _d(ivar)), "prom_expose_set")
         self._ex_shape = (n_exp, F.shape[1], n_pix)
@@ -624,6 +633,51 @@ class Device:
         ms = C.c_double(0.0)
         self._check(self.lib.prom_expose_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_expose_kernel_ms")
         return float(ms.value)
+
+    # ---- detrended exposures (prom_hip.h "detrended exposures on the device") ------------------
+    def detrend_set(self, U, W, key=None) -> None:
+        """prom_detrend_set: the filter of the resident exposure table: U [n_exp][n_comp] and W
+        [n_comp][n_exp][n_pix] in the device's pixel order, both finite, 1 <= n_comp <= 16.  ``key``: any value the
+        caller keeps in ``detrend_key`` to skip a later upload of the same filter."""
+        U, W = _f64(U), _f64(W)
+        if U.ndim != 2:
+            raise ValueError("detrend_set: U must be [n_exp][n_comp]")
+        n_exp, n_comp = U.shape
+        n_pix = (self._ex_shape or (0, 0, 0))[2]
+        if self._ex_shape is not None and W.shape != (n_comp, n_exp, n_pix):
+            raise ValueError("detrend_set: W must be [n_comp][n_exp][n_pix] of the resident exposure table")
+        self._dt_key = None
+        self._check(self.lib.prom_detrend_set(self.h, n_exp, n_comp, _d(U), _d(W)), "prom_detrend_set")
+        self._dt_key = key
+
+    @property
+    def detrend_key(self):
+        """The ``key`` of the filter resident on the context (None: none, or set without a key)."""
+        return self._dt_key
+
+    def transit_expose_detrended(self, moments: bool = True, model: bool = False):
+        """prom_transit_expose_detrended over the last run's R: (moments [n_exp][n_trial][7], n_used
+        [n_exp][n_trial], filtered model [n_exp][n_trial][n_pix]), None for what was not asked."""
+        out, ptr = self._expose_outputs(moments, model)
+        self._check(self.lib.prom_transit_expose_detrended(self.h, *ptr), "prom_transit_expose_detrended")
+        return out
+
+    def spectrum_expose_detrended(self, wav, R, moments: bool = True, model: bool = False):
+        """prom_spectrum_expose_detrended of R[n_orb][n_wav] on the ascending grid wav: (moments, n_used, model)."""
+        wav, R = _f64(wav), _f64(R)
+        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
+            raise ValueError("spectrum_expose_detrended: R must be [n_orb][n_wav]")
+        out, ptr = self._expose_outputs(moments, model)
+        self._check(self.lib.prom_spectrum_expose_detrended(self.h, R.shape[0], len(wav), _d(wav), _d(R), *ptr),
+                    "prom_spectrum_expose_detrended")
+        return out
+
+    def detrend_kernel_ms(self, n_runs: int = 20):
+        """prom_detrend_kernel_ms: mean device durations [ms] of (k_detrend, k_model_moments) for the last detrended
+        call."""
+        ms = (C.c_double * 2)(0.0, 0.0)
+        self._check(self.lib.prom_detrend_kernel_ms(self.h, int(n_runs), ms), "prom_detrend_kernel_ms")
+        return float(ms[0]), float(ms[1])
 
     # ---- stellar disk -----------------------------------------------------------------------
     def star_disk_flux(self, table_id: int, shift, clv, rho, dphi: float, drho: float, wavelength) -> np.ndarray:

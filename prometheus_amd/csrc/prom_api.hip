@@ -13,6 +13,7 @@
 #include "prom_internal.h"
 #include "tw_stage.h"
 #include "vmap_index.h"
+#include "detrend_index.h"
 
 using prom::DevBuf;
 using prom::Error;
@@ -2097,6 +2098,7 @@ int32_t prom_expose_set(prom_ctx* ctx, int32_t n_exp, int32_t n_trial, int32_t n
     prom::ExDev& ex = ctx->ex;
     const prom::ObsDev& ob = ctx->obs;
     ex.set = false;
+    ex.dt_set = ex.dt_ran = false;   // a filter belongs to the table it was set for
     ex.last_wav = ex.last_R = nullptr;
     PROM_REQUIRE(n_exp >= 1 && n_exp <= 65535 && n_trial >= 1 && n_trial <= (1 << 24) && n_tap >= 1 &&
                      n_tap <= (1 << 16) && row && a && F,
@@ -2174,6 +2176,7 @@ static void expose_on(prom_ctx* ctx, hipStream_t st, const double* wav, const do
   ex.last_wav = wav;
   ex.last_R = R;
   ex.last_n_wav = (int32_t)n_wav;
+  ex.dt_ran = false;
   if (mom_out) download(mom_out, ex.mom, 7 * n, st);
   if (n_used_out) download(n_used_out, ex.n_used, n, st);
   if (model_out) download(model_out, ex.model, nm, st);
@@ -2239,6 +2242,160 @@ int32_t prom_expose_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
       sum += ms;
     }
     *ms_out = scale * sum / n_runs;
+  });
+}
+
+// ------------------------------------------------------------------------------ detrended exposures
+int32_t prom_detrend_set(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, const double* U, const double* W) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    ex.dt_set = ex.dt_ran = false;
+    if (!ex.set || !ctx->obs.set || ctx->obs.n_orb != ex.n_orb)
+      throw Error(PROM_E_STATE, "prom_detrend_set: no exposure table on the context (prom_expose_set)");
+    PROM_REQUIRE(n_exp == ex.n_exp, "prom_detrend_set: n_exp differs from the exposure table's");
+    PROM_REQUIRE(n_comp >= 1 && n_comp <= prom::kDtMaxComp, "prom_detrend_set: n_comp must lie in [1, 16]");
+    const int64_t nu = (int64_t)n_exp * n_comp, nw = nu * ctx->obs.n_pix;
+    PROM_REQUIRE(U && (nw == 0 || W), "prom_detrend_set: U and W missing");
+    for (int64_t i = 0; i < nu; ++i) PROM_REQUIRE(obs_finite(U[i]), "prom_detrend_set: U must be finite");
+    for (int64_t i = 0; i < nw; ++i) PROM_REQUIRE(obs_finite(W[i]), "prom_detrend_set: W must be finite");
+    const hipStream_t st = ctx->stream;
+    upload(ex.U, U, nu, st);
+    upload(ex.W, W, nw, st);
+    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
+    ex.n_comp = n_comp;
+    ex.dt_set = true;
+  });
+}
+
+// the moments of the model in ex.model, in batches of whole trial groups (ev: events around the first batch's
+// k_model_moments)
+static void moments_launch(prom_ctx* ctx, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+  prom::ExDev& ex = ctx->ex;
+  const prom::ObsDev& ob = ctx->obs;
+  const int32_t n_chunks = prom::vm_chunks(ob.n_pix), n_groups = prom::vm_groups(ex.n_trial);
+  const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, n_chunks, n_groups);
+  const int32_t nb_max = std::min(bg * prom::kVmTrials, ex.n_trial);
+  ex.part.ensure(sizeof(double) * (size_t)prom::vm_part_doubles(ex.n_exp, nb_max, n_chunks));
+  static const bool debug = std::getenv("PROM_DEBUG") != nullptr;
+  if (debug)
+    std::fprintf(stderr, "prom: detrended moments: %d trials in %d groups, %d batches of up to %d groups, %d chunks\n",
+                 ex.n_trial, n_groups, (n_groups + bg - 1) / bg, bg, n_chunks);
+  for (int32_t g = 0; g < n_groups; g += bg) {
+    const int32_t j_first = prom::vm_group_first(g), nb = std::min(nb_max, ex.n_trial - j_first);
+    prom::launch_model_moments(st, ex.model.as<double>(), ex.flag.as<uint8_t>(), ex.data.as<double>(),
+                               ex.ivar.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, j_first, nb, ex.part.as<double>(),
+                               g == 0 ? ev0 : nullptr, g == 0 ? ev1 : nullptr);
+    prom::launch_vmap_reduce(st, ex.part.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, j_first, nb, ex.mom.as<double>(),
+                             ex.n_used.as<int64_t>());
+  }
+}
+
+// the unfiltered model of the whole table into ex.model (k_expose without moments), then the filter in place
+static void detrend_model(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int32_t n_wav,
+                          hipEvent_t ev0, hipEvent_t ev1) {
+  prom::ExDev& ex = ctx->ex;
+  expose_launch(ctx, st, wav, R, n_wav, false, ex.model.as<double>(), nullptr, nullptr);
+  prom::launch_detrend(st, ex.model.as<double>(), ex.U.as<double>(), ex.W.as<double>(), ex.flag.as<uint8_t>(),
+                       ex.n_exp, ex.n_comp, ex.n_trial, ctx->obs.n_pix, ev0, ev1);
+}
+
+// the shared tail of the two detrended calls, on stream st
+static void detrend_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav,
+                       double* mom_out, int64_t* n_used_out, double* model_out) {
+  prom::ExDev& ex = ctx->ex;
+  const int64_t n = (int64_t)ex.n_exp * ex.n_trial;
+  if (ctx->obs.n_pix == 0) {   // no pixel: every moment 0 and no model value
+    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
+    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
+    return;
+  }
+  if (!mom_out && !n_used_out && !model_out) return;
+  const double nan = std::nan("");
+  const int64_t nm = n * ctx->obs.n_pix;
+  ex.q.ensure(sizeof(double) * (size_t)n_wav);
+  try {   // the whole table's model is resident at once: it is not batched
+    ex.model.ensure(sizeof(double) * (size_t)nm);
+  } catch (const Error& err) {
+    throw Error(err.code, std::string(err.what()) + ": the detrended exposures keep the model of all " +
+                              std::to_string(ex.n_trial) + " trials in device memory; give fewer trials per call");
+  }
+  ex.flag.ensure((size_t)ex.n_trial * ctx->obs.n_pix);
+  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
+  detrend_model(ctx, st, wav, R, (int32_t)n_wav, nullptr, nullptr);
+  if (mom_out || n_used_out) moments_launch(ctx, st, nullptr, nullptr);
+  ex.last_wav = wav;
+  ex.last_R = R;
+  ex.last_n_wav = (int32_t)n_wav;
+  ex.dt_ran = true;
+  if (mom_out) download(mom_out, ex.mom, 7 * n, st);
+  if (n_used_out) download(n_used_out, ex.n_used, n, st);
+  if (model_out) download(model_out, ex.model, nm, st);
+  PROM_HIP(hipStreamSynchronize(st));
+}
+
+static void detrend_check(prom_ctx* ctx, const char* who) {
+  expose_check(ctx, who);
+  if (!ctx->ex.dt_set)
+    throw Error(PROM_E_STATE, std::string(who) + ": no filter on the context (prom_detrend_set; a later "
+                                                 "prom_expose_set, or whatever drops the exposure table, drops it)");
+}
+
+int32_t prom_transit_expose_detrended(prom_ctx* ctx, double* mom_out, int64_t* n_used_out, double* model_out) {
+  return guarded(ctx, [&] {
+    prom::TransitDev& tr = ctx->tr;
+    detrend_check(ctx, "prom_transit_expose_detrended");
+    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose_detrended: no completed run");
+    if (ctx->ex.n_orb != tr.n_orb)
+      throw Error(PROM_E_STATE, "prom_transit_expose_detrended: the exposure table has another n_orb");
+    detrend_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, mom_out,
+               n_used_out, model_out);
+  });
+}
+
+int32_t prom_spectrum_expose_detrended(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                       double* mom_out, int64_t* n_used_out, double* model_out) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    detrend_check(ctx, "prom_spectrum_expose_detrended");
+    PROM_REQUIRE(n_orb == ex.n_orb, "prom_spectrum_expose_detrended: n_orb differs from the observation's");
+    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_expose_detrended: bad spectrum");
+    for (int64_t w = 0; w < n_wav; ++w)
+      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
+                   "prom_spectrum_expose_detrended: wavelengths must be finite and ascending");
+    const hipStream_t st = ctx->stream;
+    ex.last_wav = ex.last_R = nullptr;   // (the uploads may move the buffers the last call read)
+    upload(ex.wav, wav, n_wav, st);
+    upload(ex.R, R, (int64_t)n_orb * n_wav, st);
+    detrend_on(ctx, st, ex.wav.as<double>(), ex.R.as<double>(), n_wav, mom_out, n_used_out, model_out);
+  });
+}
+
+int32_t prom_detrend_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_detrend_kernel_ms: bad arguments");
+    if (!ex.set || !ex.dt_set || !ex.dt_ran || !ctx->obs.set || !ex.last_wav || ctx->obs.n_pix == 0)
+      throw Error(PROM_E_STATE, "prom_detrend_kernel_ms: no detrended call to repeat");
+    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
+    const hipStream_t st = ctx->stream;
+    // the filter works in place, so every repetition forms the unfiltered model again (untimed) before k_detrend
+    // (timed, the whole table); k_model_moments of the first batch, scaled to the table by trial count
+    const int32_t n_groups = prom::vm_groups(ex.n_trial);
+    const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, prom::vm_chunks(ctx->obs.n_pix), n_groups);
+    const double scale = (double)ex.n_trial / (double)std::min(bg * prom::kVmTrials, ex.n_trial);
+    double sum[2] = {0.0, 0.0};
+    for (int32_t r = 0; r < n_runs; ++r) {
+      detrend_model(ctx, st, ex.last_wav, ex.last_R, ex.last_n_wav, ctx->ev[0], ctx->ev[1]);
+      moments_launch(ctx, st, ctx->ev[2], ctx->ev[3]);
+      PROM_HIP(hipStreamSynchronize(st));
+      float ms = 0.0f;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      sum[0] += ms;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+      sum[1] += ms;
+    }
+    ms_out[0] = sum[0] / n_runs;
+    ms_out[1] = scale * sum[1] / n_runs;
   });
 }
 

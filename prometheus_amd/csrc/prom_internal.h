@@ -455,6 +455,12 @@ struct ExDev {
   const double* last_wav = nullptr;
   const double* last_R = nullptr;
   int32_t last_n_wav = 0;
+  // The filter of the detrended exposures (prom_detrend_set): it lives while the table it was set for does, so it
+  // counts only while `set` holds, and prom_expose_set clears dt_set.
+  bool dt_set = false;
+  int32_t n_comp = 0;
+  DevBuf U, W, flag;                      // [n_exp][n_comp], [n_comp][n_exp][n_pix], [n_trial][n_pix] bytes
+  bool dt_ran = false;                    // the last call on last_wav / last_R was a detrended one
 };
 
 }  // namespace prom
@@ -580,6 +586,14 @@ void launch_expose(hipStream_t s, const double* wav, const double* q, const doub
                    const double* sig, double k, const int32_t* row, const double* wgt, const double* F,
                    const double* data, const double* ivar, int32_t n_pix, int32_t n_exp, int32_t n_trial, int32_t n_tap,
                    int32_t j_first, int32_t nb, double* part, double* model, hipEvent_t ev0, hipEvent_t ev1);
+// detrended exposures (prom_detrend.hip): model[n_exp][n_trial][n_pix] filtered in place with U[n_exp][n_comp] and
+// W[n_comp][n_exp][n_pix], flag[n_trial][n_pix] = the column is filterable; then the moments of trials
+// [j_first, j_first + nb) of that model into the batch's partial records, as launch_expose's
+void launch_detrend(hipStream_t s, double* model, const double* U, const double* W, uint8_t* flag, int32_t n_exp,
+                    int32_t n_comp, int32_t n_trial, int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1);
+void launch_model_moments(hipStream_t s, const double* model, const uint8_t* flag, const double* data,
+                          const double* ivar, int32_t n_pix, int32_t n_exp, int32_t n_trial, int32_t j_first,
+                          int32_t nb, double* part, hipEvent_t ev0, hipEvent_t ev1);
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

@@ -155,6 +155,127 @@ class Exposures:
         return self._pixels[n_orb]
 
 
+def _weights_of(data, err):
+    """(data with masked entries 0, inverse variances with masked entries 0) of data and its standard error."""
+    d = np.asarray(data, dtype=np.float64)
+    e = np.broadcast_to(np.asarray(err, dtype=np.float64), d.shape)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ok = np.isfinite(d) & np.isfinite(e) & (e > 0)
+        return np.where(ok, d, 0.0), np.where(ok, 1.0 / (e * e), 0.0)
+
+
+def sysrem(data, err, n_comp: int, n_iter: int = 30, ones: bool = False):
+    """SYSREM (Tamuz, Mazeh & Zucker 2005) on the host, once per data set: ``n_comp`` times the weighted rank-one fit
+    a[e] c[p] that minimises sum (r - a c)^2 / err^2 over the residuals r is found by ``n_iter`` alternating
+    least-squares steps (c from a, then a from c; a starts at ones and is scaled to unit length, the scale going to
+    c) and subtracted.  ``data`` and ``err`` are [n_exp][n_pix] (err anything that broadcasts); an entry with
+    non-finite data or err, or err <= 0, has no weight.  Returns (U [n_exp][n_comp], the cleaned data, masked entries
+    as they came).  With ``ones`` every pixel's weighted mean over the exposures is removed first and U gets a leading
+    column of ones for it: U is then [n_exp][n_comp + 1].  U is the basis the model must be filtered with
+    (filter_weights, Detrend)."""
+    d0 = np.asarray(data, dtype=np.float64)
+    if d0.ndim != 2 or d0.shape[0] < 1:
+        raise ValueError("sysrem: data must be [n_exp][n_pix]")
+    n_comp, n_iter = int(n_comp), int(n_iter)
+    if n_comp < 0 or n_iter < 1 or n_comp + bool(ones) < 1:
+        raise ValueError("sysrem: n_comp >= 1 (0 with ones) and n_iter >= 1")
+    try:
+        r, iv = _weights_of(d0, err)
+    except ValueError:
+        raise ValueError("sysrem: err must broadcast to data") from None
+    cols = []
+
+    def fit_c(a):
+        den = (iv * (a * a)[:, None]).sum(axis=0)
+        return np.where(den > 0, (iv * r * a[:, None]).sum(axis=0) / np.where(den > 0, den, 1.0), 0.0)
+
+    if ones:
+        a = np.ones(d0.shape[0])
+        r = r - a[:, None] * fit_c(a)[None, :]
+        cols.append(a)
+    for _ in range(n_comp):
+        a = np.ones(d0.shape[0]) / np.sqrt(d0.shape[0])
+        c = fit_c(a)
+        for _ in range(n_iter):
+            den = (iv * (c * c)[None, :]).sum(axis=1)
+            a = np.where(den > 0, (iv * r * c[None, :]).sum(axis=1) / np.where(den > 0, den, 1.0), 0.0)
+            norm = np.sqrt((a * a).sum())
+            if not norm > 0:
+                break
+            a = a / norm
+            c = fit_c(a)
+        r = r - a[:, None] * c[None, :]
+        cols.append(a)
+    return np.ascontiguousarray(np.stack(cols, axis=1)), np.where(iv > 0, r, d0)
+
+
+def filter_weights(U, ivar) -> np.ndarray:
+    """W[n_comp][n_exp][n_pix] of the basis U[n_exp][n_comp] under the inverse variances ivar[n_exp][n_pix]: at pixel
+    p, W_p = (U^T L_p U)^-1 U^T L_p with L_p = diag(ivar[:, p]), the weighted least-squares pseudo-inverse, so that
+    m' = m - U (W_p m) removes from a column m what a fit of the basis finds in it.  Entries with ivar = 0 (or not
+    finite, or < 0) are exactly 0.  A pixel whose normal matrix U^T L_p U is singular (its smallest eigenvalue not
+    above n_comp 2^-52 times its largest: too few weighted exposures, or dependent columns) gets W = 0: it is then
+    filtered by nothing and stays usable."""
+    U = np.asarray(U, dtype=np.float64)
+    iv = np.asarray(ivar, dtype=np.float64)
+    if U.ndim != 2 or U.shape[1] < 1 or iv.ndim != 2 or iv.shape[0] != U.shape[0]:
+        raise ValueError("filter_weights: U must be [n_exp][n_comp] and ivar [n_exp][n_pix]")
+    if not np.all(np.isfinite(U)):
+        raise ValueError("filter_weights: U must be finite")
+    n_exp, K = U.shape
+    with np.errstate(invalid="ignore"):
+        iv = np.where(np.isfinite(iv) & (iv > 0), iv, 0.0)
+    B = U.T[None, :, :] * iv.T[:, None, :]                     # [n_pix][K][n_exp]: U^T L_p
+    N = B @ U                                                  # [n_pix][K][K]
+    lam = np.linalg.eigvalsh(N)
+    good = np.isfinite(lam).all(axis=1) & (lam[:, 0] > K * 2.0 ** -52 * lam[:, -1])
+    W = np.zeros((iv.shape[1], K, n_exp))
+    if good.any():
+        W[good] = np.linalg.solve(N[good], B[good])
+    W[~np.isfinite(W).all(axis=(1, 2))] = 0.0
+    W = np.ascontiguousarray(W.transpose(1, 2, 0))
+    W[:, iv == 0.0] = 0.0
+    return W
+
+
+class Detrend:
+    """The filter of Transit.expose(detrend=...): the basis ``U`` [n_exp][n_comp] (1 <= n_comp <= 16) the data of
+    ``exposures`` were cleaned with (sysrem) and its pseudo-inverse per pixel ``W`` [n_comp][n_exp][n_pix] in the
+    caller's pixel order (None: filter_weights with the exposures' inverse variances).  The model of every trial is
+    filtered per pixel column, m' = m - U (W_p m), before it meets the data (include/prom_hip.h, "detrended exposures
+    on the device").  Sorting W into the device's pixel order and the content key that lets a device skip the upload
+    are computed once here; the arrays are copied.  ValueError for a bad shape or a non-finite value."""
+
+    MAX_COMP = 16
+
+    def __init__(self, exposures: Exposures, U, W=None):
+        from .gasProperties import _content_fingerprint
+        if not isinstance(exposures, Exposures):
+            raise TypeError("Detrend: exposures must be an observation.Exposures")
+        u = np.array(U, dtype=np.float64)
+        if u.ndim != 2 or u.shape[0] != exposures.n_exp:
+            raise ValueError("Detrend: U must be [n_exp][n_comp] with n_exp = %d" % exposures.n_exp)
+        if not 1 <= u.shape[1] <= self.MAX_COMP:
+            raise ValueError("Detrend: n_comp must lie in [1, %d]" % self.MAX_COMP)
+        if not np.all(np.isfinite(u)):
+            raise ValueError("Detrend: U must be finite")
+        self.U = np.ascontiguousarray(u)
+        self.n_exp, self.n_comp = self.U.shape
+        shape = (self.n_comp, self.n_exp, exposures.instrument.n_pix)
+        if W is None:
+            w = filter_weights(self.U, exposures.ivar)          # (the exposures' ivar is in the device's order)
+        else:
+            w = np.asarray(W, dtype=np.float64)
+            if w.shape != shape:
+                raise ValueError("Detrend: W must be [n_comp][n_exp][n_pix] = [%d][%d][%d]" % shape)
+            w = exposures.instrument.sort(w)
+        if not np.all(np.isfinite(w)):
+            raise ValueError("Detrend: W must be finite")
+        self.W = np.ascontiguousarray(w)                        # what the device sees
+        self.exposures_key = exposures.key
+        self.key = ("detrend", exposures.key) + _content_fingerprint(self.U, self.W)
+
+
 def model_spectrum(num, den) -> np.ndarray:
     """M = num / den; NaN where den == 0 (no model coverage)."""
     num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
