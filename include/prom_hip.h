@@ -478,6 +478,70 @@ int32_t prom_spectrum_expose_detrended(prom_ctx* ctx, int32_t n_orb, int64_t n_w
  * again (untimed) before it.  PROM_E_STATE when there is no such call. */
 int32_t prom_detrend_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
 
+/* ---- high-pass filtered exposures on the device -----------------------------------------------
+ * High-resolution data never keep their continuum: each exposure of each echelle order has a smooth function along
+ * its pixels (a Gaussian or box running mean, tens to hundreds of pixels wide) subtracted from it or divided out of
+ * it, and SYSREM runs after that.  The model goes through the same two steps in the same order before it meets the
+ * data.  The high-pass couples the pixels of one exposure inside one order.  All float64; the roundings named here are
+ * part of the definition.
+ *
+ *   inputs               the resident observation and exposure table (prom_expose_set), a spectrum over the whole
+ *                        grid, and a resident high-pass:
+ *                          segments (the orders)      n_seg >= 1, seg_first[n_seg + 1] and perm[n_pix], both int32:
+ *                                                     seg_first strictly ascending from 0 to n_pix (no segment is
+ *                                                     empty), perm a permutation of 0 .. n_pix - 1; position i of
+ *                                                     segment s is the device pixel perm[seg_first[s] + i]
+ *                          taps                       half_width h, 0 <= h <= 512, and g[h + 1], every entry finite
+ *                                                     and >= 0, g[0] > 0: g[d] is the weight at distance d
+ *                          mode                       0 subtracts, 1 divides
+ *   unfiltered model     M[e][j][p] is prom_spectrum_expose's model_out value, bit for bit
+ *   smooth model         in a segment of length n, at position i of one (e, j), over the window
+ *                        i' in [max(0, i - h), min(n - 1, i + h)] in ascending i': num starts at +0 and adds
+ *                        fl(g[|i - i'|] M_i') for every i' whose M is not NaN; den starts at +0 and adds g[|i - i'|]
+ *                        for the same i'.  Every product and every sum is rounded on its own, there is no fused
+ *                        multiply-add, and a plain numpy loop gives the same bits.  A NaN value is skipped altogether
+ *                        (adding +0 for it gives the same bits: num and den are never -0, and a kernel may rely on
+ *                        that).  B_i = fl(num / den)
+ *   filtered model       M'_i = fl(M_i - B_i) in mode 0, fl(M_i / B_i) in mode 1.  M'_i is NaN exactly where M_i is
+ *                        NaN: a valid M_i always has den >= g[0] > 0; what IEEE gives otherwise stands (B = 0 under
+ *                        division, an infinity).  An interior window without a NaN sees the same sequence of g for
+ *                        every i, so a kernel may form that den once: the bits are the same
+ *   then                 on request (detrend = 1) the resident SYSREM filter runs on M' exactly as defined under
+ *                        "detrended exposures on the device", with M' in the place of M
+ *   used pixels          (e, j, p) is used when ivar[e][p] is finite and > 0, data[e][p] is finite, the final model
+ *                        value is not NaN and, with the SYSREM filter, the column is filterable
+ *   moments              the seven moments and n_used in the map's shape, as for the detrended exposures; with no
+ *                        used pixel zeros
+ *   models on request    model[e][j][p] = the final model
+ *   independence         the numbers of (e, j) depend only on the spectrum, the pixels, exposure e's live taps and
+ *                        column j's factors (with the SYSREM filter those of all exposures, as there), the high-pass,
+ *                        data and ivar: not on n_trial, j's position, other trials or the launcher's batches.  Two
+ *                        calls agree bit for bit; there are no floating-point atomics
+ *   degenerate cases     every segment of length 1, or h = 0: B = fl(fl(g[0] M) / g[0]), which is M when g[0] is a
+ *                        power of two (gaussian_taps and box_taps give 1): mode 0 gives +0 wherever M is valid, mode 1
+ *                        gives 1 wherever M is valid and not 0 */
+
+/* Make the high-pass resident.  PROM_E_STATE without a resident exposure table; PROM_E_ARG when n_pix differs from the
+ * observation's or a rule above is broken (with n_pix = 0: n_seg = 1 and seg_first = {0, 0}).  prom_expose_set, and
+ * whatever drops the exposure table, drops the high-pass (the calls below then fail with PROM_E_STATE). */
+int32_t prom_highpass_set(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32_t* seg_first, const int32_t* perm,
+                          int32_t half_width, const double* g, int32_t mode);
+/* The high-pass filtered exposures over the last run's R on its stream: the outputs, NULL rules and checks of
+ * prom_transit_expose_detrended, n_pix = 0 gives zeros.  detrend is 0 or 1 (otherwise PROM_E_ARG); with 1 the
+ * resident filter of prom_detrend_set follows the high-pass, and PROM_E_STATE when there is none.  The model of the
+ * whole table lies in device memory at once, as for the detrended exposures: PROM_E_NOMEM when it does not fit (the
+ * remedy is fewer trials per call).  A workgroup of k_highpass owns one (exposure, trial, segment):
+ * n_exp n_trial n_seg >= 2^31 is PROM_E_ARG. */
+int32_t prom_transit_expose_highpass(prom_ctx* ctx, int32_t detrend, double* mom_out, int64_t* n_used_out,
+                                     double* model_out);
+/* The same for a spectrum the caller supplies (the checks of prom_spectrum_expose). */
+int32_t prom_spectrum_expose_highpass(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                      int32_t detrend, double* mom_out, int64_t* n_used_out, double* model_out);
+/* Measurement aid (tools/highpass_bench.py), not for callers: ms_out[0] is the mean device duration in milliseconds of
+ * k_highpass over the whole table, over n_runs repetitions of the last high-pass call.  The filter works in place, so
+ * each repetition forms the unfiltered model again (untimed) before it.  PROM_E_STATE when there is no such call. */
+int32_t prom_highpass_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
+
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop
  * events on its own dispatch packet (groups of kernels: the first start to the last stop).  ms_out[k] is

@@ -138,6 +138,12 @@ SIGNATURES = {
     "prom_spectrum_expose_detrended": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, _dp,
                                                    C.POINTER(C.c_int64), _dp]),
     "prom_detrend_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
+    "prom_highpass_set": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                      C.c_int32, _dp, C.c_int32]),
+    "prom_transit_expose_highpass": (C.c_int32, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_int64), _dp]),
+    "prom_spectrum_expose_highpass": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _dp,
+                                                  C.POINTER(C.c_int64), _dp]),
+    "prom_highpass_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -262,6 +268,7 @@ class Device:
         self._ex_shape = None
         self._ex_key = None
         self._dt_key = None
+        self._hp_key = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -392,6 +399,7 @@ class Device:
             self._vm_shape = self._vm_key = None     # ... and the trial table with it
             self._ex_shape = self._ex_key = None     # ... and the exposure table
             self._dt_key = None                      # ... with its filter
+            self._hp_key = None                      # ... and its high-pass
         self._n_atoms = prob.n_atoms
         self._n_pr = prob.struct.n_pr
 
@@ -471,6 +479,7 @@ class Device:
         self._vm_shape = self._vm_key = None   # the library drops the trial table with the observation it was set for
         self._ex_shape = self._ex_key = None   # ... and the exposure table
         self._dt_key = None                    # ... with its filter
+        self._hp_key = None                    # ... and its high-pass
         self._check(self.lib.prom_observe_set(self.h, n_pix, _d(lam), _d(sig), float(k), n_orb,
                                               _d(f) if f is not None else None,
                                               _d(data) if data is not None else None,
@@ -589,6 +598,7 @@ class Device:
             raise ValueError("expose_set: data and ivar must be [n_exp][n_pix] of the resident observation")
         self._ex_shape = self._ex_key = None
         self._dt_key = None   # the library drops the filter with the table it was set for
+        self._hp_key = None   # ... and the high-pass
         self._check(self.lib.prom_expose_set(self.h, n_exp, F.shape[1], n_tap, rows.ctypes.data_as(C.POINTER(C.c_int32)),
                                              _d(a), _d(F), _d(data), _d(ivar)), "prom_expose_set")
         self._ex_shape = (n_exp, F.shape[1], n_pix)
@@ -678,6 +688,54 @@ class Device:
         ms = (C.c_double * 2)(0.0, 0.0)
         self._check(self.lib.prom_detrend_kernel_ms(self.h, int(n_runs), ms), "prom_detrend_kernel_ms")
         return float(ms[0]), float(ms[1])
+
+    # ---- high-pass filtered exposures (prom_hip.h "high-pass filtered exposures on the device") ----
+    def highpass_set(self, seg_first, perm, g, mode: int = 0, key=None) -> None:
+        """prom_highpass_set: the high-pass of the resident exposure table: the segments seg_first [n_seg + 1] and perm
+        [n_pix] (int32; position i of segment s is the device pixel perm[seg_first[s] + i]), the taps g
+        [half_width + 1] (finite, >= 0, g[0] > 0, half_width <= 512) and mode (0 subtracts, 1 divides).  ``key``: any
+        value the caller keeps in ``highpass_key`` to skip a later upload of the same high-pass."""
+        seg = np.ascontiguousarray(seg_first, dtype=np.int32)
+        pm = np.ascontiguousarray(perm, dtype=np.int32)
+        g = _f64(g)
+        if seg.ndim != 1 or len(seg) < 2 or pm.ndim != 1 or g.ndim != 1 or len(g) < 1:
+            raise ValueError("highpass_set: seg_first must be [n_seg + 1], perm [n_pix] and g [half_width + 1]")
+        self._hp_key = None
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.prom_highpass_set(self.h, len(pm), len(seg) - 1, seg.ctypes.data_as(ip),
+                                               pm.ctypes.data_as(ip), len(g) - 1, _d(g), int(mode)),
+                    "prom_highpass_set")
+        self._hp_key = key
+
+    @property
+    def highpass_key(self):
+        """The ``key`` of the high-pass resident on the context (None: none, or set without a key)."""
+        return self._hp_key
+
+    def transit_expose_highpass(self, detrend: bool = False, moments: bool = True, model: bool = False):
+        """prom_transit_expose_highpass over the last run's R: (moments [n_exp][n_trial][7], n_used [n_exp][n_trial],
+        final model [n_exp][n_trial][n_pix]), None for what was not asked.  ``detrend``: the resident filter of
+        detrend_set runs after the high-pass."""
+        out, ptr = self._expose_outputs(moments, model)
+        self._check(self.lib.prom_transit_expose_highpass(self.h, int(detrend), *ptr), "prom_transit_expose_highpass")
+        return out
+
+    def spectrum_expose_highpass(self, wav, R, detrend: bool = False, moments: bool = True, model: bool = False):
+        """prom_spectrum_expose_highpass of R[n_orb][n_wav] on the ascending grid wav: (moments, n_used, model)."""
+        wav, R = _f64(wav), _f64(R)
+        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
+            raise ValueError("spectrum_expose_highpass: R must be [n_orb][n_wav]")
+        out, ptr = self._expose_outputs(moments, model)
+        self._check(self.lib.prom_spectrum_expose_highpass(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(detrend),
+                                                           *ptr), "prom_spectrum_expose_highpass")
+        return out
+
+    def highpass_kernel_ms(self, n_runs: int = 20) -> float:
+        """prom_highpass_kernel_ms: mean device duration [ms] of k_highpass over the whole table for the last
+        high-pass call."""
+        ms = C.c_double(0.0)
+        self._check(self.lib.prom_highpass_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_highpass_kernel_ms")
+        return float(ms.value)
 
     # ---- stellar disk -----------------------------------------------------------------------
     def star_disk_flux(self, table_id: int, shift, clv, rho, dphi: float, drho: float, wavelength) -> np.ndarray:

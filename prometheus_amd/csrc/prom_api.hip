@@ -14,6 +14,7 @@
 #include "tw_stage.h"
 #include "vmap_index.h"
 #include "detrend_index.h"
+#include "highpass_index.h"
 
 using prom::DevBuf;
 using prom::Error;
@@ -2099,6 +2100,7 @@ int32_t prom_expose_set(prom_ctx* ctx, int32_t n_exp, int32_t n_trial, int32_t n
     const prom::ObsDev& ob = ctx->obs;
     ex.set = false;
     ex.dt_set = ex.dt_ran = false;   // a filter belongs to the table it was set for
+    ex.hp_set = ex.hp_ran = false;   // ... and so does a high-pass
     ex.last_wav = ex.last_R = nullptr;
     PROM_REQUIRE(n_exp >= 1 && n_exp <= 65535 && n_trial >= 1 && n_trial <= (1 << 24) && n_tap >= 1 &&
                      n_tap <= (1 << 16) && row && a && F,
@@ -2176,7 +2178,7 @@ static void expose_on(prom_ctx* ctx, hipStream_t st, const double* wav, const do
   ex.last_wav = wav;
   ex.last_R = R;
   ex.last_n_wav = (int32_t)n_wav;
-  ex.dt_ran = false;
+  ex.dt_ran = ex.hp_ran = false;
   if (mom_out) download(mom_out, ex.mom, 7 * n, st);
   if (n_used_out) download(n_used_out, ex.n_used, n, st);
   if (model_out) download(model_out, ex.model, nm, st);
@@ -2327,6 +2329,7 @@ static void detrend_on(prom_ctx* ctx, hipStream_t st, const double* wav, const d
   ex.last_R = R;
   ex.last_n_wav = (int32_t)n_wav;
   ex.dt_ran = true;
+  ex.hp_ran = false;
   if (mom_out) download(mom_out, ex.mom, 7 * n, st);
   if (n_used_out) download(n_used_out, ex.n_used, n, st);
   if (model_out) download(model_out, ex.model, nm, st);
@@ -2396,6 +2399,169 @@ int32_t prom_detrend_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
     }
     ms_out[0] = sum[0] / n_runs;
     ms_out[1] = scale * sum[1] / n_runs;
+  });
+}
+
+// ------------------------------------------------------------------------------ high-pass filtered exposures
+int32_t prom_highpass_set(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32_t* seg_first, const int32_t* perm,
+                          int32_t half_width, const double* g, int32_t mode) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    ex.hp_set = ex.hp_ran = false;
+    if (!ex.set || !ctx->obs.set || ctx->obs.n_orb != ex.n_orb)
+      throw Error(PROM_E_STATE, "prom_highpass_set: no exposure table on the context (prom_expose_set)");
+    PROM_REQUIRE(n_pix == ctx->obs.n_pix, "prom_highpass_set: n_pix differs from the observation's");
+    PROM_REQUIRE(n_seg >= 1 && seg_first && (n_pix == 0 || perm), "prom_highpass_set: segments missing");
+    PROM_REQUIRE(half_width >= 0 && half_width <= prom::kHpMaxHalf && g,
+                 "prom_highpass_set: half_width must lie in [0, 512]");
+    PROM_REQUIRE(mode == 0 || mode == 1, "prom_highpass_set: mode must be 0 (subtract) or 1 (divide)");
+    if (n_pix == 0) {   // no pixel: no segment can hold one; the calls give zeros
+      PROM_REQUIRE(n_seg == 1 && seg_first[0] == 0 && seg_first[1] == 0,
+                   "prom_highpass_set: without pixels seg_first must be {0, 0}");
+    } else {
+      PROM_REQUIRE(n_seg <= n_pix && seg_first[0] == 0 && seg_first[n_seg] == n_pix,
+                   "prom_highpass_set: seg_first must run from 0 to n_pix");
+      for (int32_t i = 0; i < n_seg; ++i)
+        PROM_REQUIRE(seg_first[i + 1] > seg_first[i], "prom_highpass_set: seg_first must be strictly ascending");
+      std::vector<char> seen((size_t)n_pix, 0);
+      for (int32_t i = 0; i < n_pix; ++i) {
+        PROM_REQUIRE(perm[i] >= 0 && perm[i] < n_pix && !seen[(size_t)perm[i]],
+                     "prom_highpass_set: perm must be a permutation of 0 .. n_pix - 1");
+        seen[(size_t)perm[i]] = 1;
+      }
+    }
+    for (int32_t d = 0; d <= half_width; ++d)
+      PROM_REQUIRE(obs_finite(g[d]) && g[d] >= 0.0, "prom_highpass_set: g must be finite and >= 0");
+    PROM_REQUIRE(g[0] > 0.0, "prom_highpass_set: g[0] must be > 0");
+    const hipStream_t st = ctx->stream;
+    upload(ex.hp_seg, seg_first, (int64_t)n_seg + 1, st);
+    upload(ex.hp_perm, perm, (int64_t)n_pix, st);
+    upload(ex.hp_g, g, (int64_t)half_width + 1, st);
+    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
+    ex.hp_n_seg = n_seg;
+    ex.hp_half = half_width;
+    ex.hp_mode = mode;
+    ex.hp_den = prom::hp_den_full(g, half_width);
+    ex.hp_set = true;
+  });
+}
+
+// the unfiltered model of the whole table into ex.model (k_expose without moments), the high-pass in place (ev:
+// events around k_highpass), then the SYSREM filter in place or every column flagged filterable
+static void highpass_model(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int32_t n_wav,
+                           int32_t detrend, hipEvent_t ev0, hipEvent_t ev1) {
+  prom::ExDev& ex = ctx->ex;
+  const int32_t n_pix = ctx->obs.n_pix;
+  expose_launch(ctx, st, wav, R, n_wav, false, ex.model.as<double>(), nullptr, nullptr);
+  prom::launch_highpass(st, ex.model.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(),
+                        ex.hp_g.as<double>(), ex.hp_half, ex.hp_den, ex.hp_mode, (int64_t)ex.n_exp * ex.n_trial,
+                        ex.hp_n_seg, n_pix, ev0, ev1);
+  if (detrend)
+    prom::launch_detrend(st, ex.model.as<double>(), ex.U.as<double>(), ex.W.as<double>(), ex.flag.as<uint8_t>(),
+                         ex.n_exp, ex.n_comp, ex.n_trial, n_pix, nullptr, nullptr);
+  else
+    PROM_HIP(hipMemsetAsync(ex.flag.as<uint8_t>(), 1, (size_t)ex.n_trial * n_pix, st));
+}
+
+// the shared tail of the two high-pass calls, on stream st
+static void highpass_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav,
+                        int32_t detrend, double* mom_out, int64_t* n_used_out, double* model_out) {
+  prom::ExDev& ex = ctx->ex;
+  const int64_t n = (int64_t)ex.n_exp * ex.n_trial;
+  if (ctx->obs.n_pix == 0) {   // no pixel: every moment 0 and no model value
+    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
+    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
+    return;
+  }
+  if (!mom_out && !n_used_out && !model_out) return;
+  if (prom::hp_workgroups(n, ex.hp_n_seg) > (((int64_t)1 << 31) - 1))   // (before anything is launched)
+    throw Error(PROM_E_ARG, "k_highpass: n_exp n_trial n_seg too large for one launch");
+  const double nan = std::nan("");
+  const int64_t nm = n * ctx->obs.n_pix;
+  ex.q.ensure(sizeof(double) * (size_t)n_wav);
+  try {   // the whole table's model is resident at once: it is not batched
+    ex.model.ensure(sizeof(double) * (size_t)nm);
+  } catch (const Error& err) {
+    throw Error(err.code, std::string(err.what()) + ": the high-pass filtered exposures keep the model of all " +
+                              std::to_string(ex.n_trial) + " trials in device memory; give fewer trials per call");
+  }
+  ex.flag.ensure((size_t)ex.n_trial * ctx->obs.n_pix);
+  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
+  highpass_model(ctx, st, wav, R, (int32_t)n_wav, detrend, nullptr, nullptr);
+  if (mom_out || n_used_out) moments_launch(ctx, st, nullptr, nullptr);
+  ex.last_wav = wav;
+  ex.last_R = R;
+  ex.last_n_wav = (int32_t)n_wav;
+  ex.dt_ran = false;
+  ex.hp_ran = true;
+  ex.hp_detrend = detrend;
+  if (mom_out) download(mom_out, ex.mom, 7 * n, st);
+  if (n_used_out) download(n_used_out, ex.n_used, n, st);
+  if (model_out) download(model_out, ex.model, nm, st);
+  PROM_HIP(hipStreamSynchronize(st));
+}
+
+static void highpass_check(prom_ctx* ctx, const char* who, int32_t detrend) {
+  expose_check(ctx, who);
+  if (!ctx->ex.hp_set)
+    throw Error(PROM_E_STATE, std::string(who) + ": no high-pass on the context (prom_highpass_set; a later "
+                                                 "prom_expose_set, or whatever drops the exposure table, drops it)");
+  if (detrend != 0 && detrend != 1) throw Error(PROM_E_ARG, std::string(who) + ": detrend must be 0 or 1");
+  if (detrend && !ctx->ex.dt_set)
+    throw Error(PROM_E_STATE, std::string(who) + ": detrend = 1 without a filter on the context (prom_detrend_set)");
+}
+
+int32_t prom_transit_expose_highpass(prom_ctx* ctx, int32_t detrend, double* mom_out, int64_t* n_used_out,
+                                     double* model_out) {
+  return guarded(ctx, [&] {
+    prom::TransitDev& tr = ctx->tr;
+    highpass_check(ctx, "prom_transit_expose_highpass", detrend);
+    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose_highpass: no completed run");
+    if (ctx->ex.n_orb != tr.n_orb)
+      throw Error(PROM_E_STATE, "prom_transit_expose_highpass: the exposure table has another n_orb");
+    highpass_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, detrend,
+                mom_out, n_used_out, model_out);
+  });
+}
+
+int32_t prom_spectrum_expose_highpass(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                      int32_t detrend, double* mom_out, int64_t* n_used_out, double* model_out) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    highpass_check(ctx, "prom_spectrum_expose_highpass", detrend);
+    PROM_REQUIRE(n_orb == ex.n_orb, "prom_spectrum_expose_highpass: n_orb differs from the observation's");
+    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_expose_highpass: bad spectrum");
+    for (int64_t w = 0; w < n_wav; ++w)
+      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
+                   "prom_spectrum_expose_highpass: wavelengths must be finite and ascending");
+    const hipStream_t st = ctx->stream;
+    ex.last_wav = ex.last_R = nullptr;   // (the uploads may move the buffers the last call read)
+    upload(ex.wav, wav, n_wav, st);
+    upload(ex.R, R, (int64_t)n_orb * n_wav, st);
+    highpass_on(ctx, st, ex.wav.as<double>(), ex.R.as<double>(), n_wav, detrend, mom_out, n_used_out, model_out);
+  });
+}
+
+int32_t prom_highpass_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_highpass_kernel_ms: bad arguments");
+    if (!ex.set || !ex.hp_set || !ex.hp_ran || !ctx->obs.set || !ex.last_wav || ctx->obs.n_pix == 0 ||
+        (ex.hp_detrend && !ex.dt_set))
+      throw Error(PROM_E_STATE, "prom_highpass_kernel_ms: no high-pass call to repeat");
+    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
+    const hipStream_t st = ctx->stream;
+    // the filter works in place, so every repetition forms the unfiltered model again (untimed) before k_highpass
+    // (timed, the whole table)
+    double sum = 0.0;
+    for (int32_t r = 0; r < n_runs; ++r) {
+      highpass_model(ctx, st, ex.last_wav, ex.last_R, ex.last_n_wav, ex.hp_detrend, ctx->ev[0], ctx->ev[1]);
+      PROM_HIP(hipStreamSynchronize(st));
+      float ms = 0.0f;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      sum += ms;
+    }
+    ms_out[0] = sum / n_runs;
   });
 }
 

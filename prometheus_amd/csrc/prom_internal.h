@@ -461,6 +461,14 @@ struct ExDev {
   int32_t n_comp = 0;
   DevBuf U, W, flag;                      // [n_exp][n_comp], [n_comp][n_exp][n_pix], [n_trial][n_pix] bytes
   bool dt_ran = false;                    // the last call on last_wav / last_R was a detrended one
+  // The high-pass of the filtered exposures (prom_highpass_set): like the filter above it lives while the table it
+  // was set for does, and prom_expose_set clears hp_set.
+  bool hp_set = false;
+  int32_t hp_n_seg = 0, hp_half = 0, hp_mode = 0;
+  double hp_den = 0.0;                    // hp_den_full of the taps
+  DevBuf hp_seg, hp_perm, hp_g;           // seg_first[n_seg + 1], perm[n_pix] (int32), g[half_width + 1]
+  bool hp_ran = false;                    // the last call on last_wav / last_R was a high-pass one ...
+  int32_t hp_detrend = 0;                 // ... with this `detrend`
 };
 
 }  // namespace prom
@@ -594,6 +602,11 @@ void launch_detrend(hipStream_t s, double* model, const double* U, const double*
 void launch_model_moments(hipStream_t s, const double* model, const uint8_t* flag, const double* data,
                           const double* ivar, int32_t n_pix, int32_t n_exp, int32_t n_trial, int32_t j_first,
                           int32_t nb, double* part, hipEvent_t ev0, hipEvent_t ev1);
+// high-pass filtered exposures (prom_highpass.hip): the n_rows = n_exp n_trial rows of model[.][n_pix] filtered in place
+// along the segments seg_first[n_seg + 1] / perm[n_pix] with the taps g[half_width + 1]; den_full is hp_den_full(g)
+void launch_highpass(hipStream_t s, double* model, const int32_t* seg_first, const int32_t* perm, const double* g,
+                     int32_t half_width, double den_full, int32_t mode, int64_t n_rows, int32_t n_seg, int32_t n_pix,
+                     hipEvent_t ev0, hipEvent_t ev1);
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

@@ -652,11 +652,12 @@ class _ExposeJob:
     """One Transit.expose call inside _integrate: the pixels and the exposure table go to the device once each while
     their content keys are unchanged, then the exposures run over the (one) chunk's R."""
 
-    def __init__(self, exposures, n_orb, want_model, detrend=None):
+    def __init__(self, exposures, n_orb, want_model, detrend=None, highpass=None):
         self.ex = exposures
         self.obs = _ObserveJob(exposures.pixels(n_orb), False)
         self.want_model = want_model
         self.dt = detrend
+        self.hp = highpass
         self.whole = False
         self.moments = self.n_used = self.model = None
 
@@ -666,10 +667,14 @@ class _ExposeJob:
             dev.expose_set(self.ex.rows, self.ex.weights, self.ex.factors, self.ex.data, self.ex.ivar, key=self.ex.key)
         if self.dt is not None and dev.detrend_key != self.dt.key:   # (a new table has dropped the filter)
             dev.detrend_set(self.dt.U, self.dt.W, key=self.dt.key)
+        if self.hp is not None and dev.highpass_key != self.hp.key:   # (likewise)
+            dev.highpass_set(self.hp.seg_first, self.hp.perm, self.hp.taps, self.hp.mode_id, key=self.hp.key)
 
     def run(self, dev, wavelength, a: int, b: int):
         if not self.whole:   # (expose refuses such a run before it starts)
             raise RuntimeError("expose: the run was split into wavelength shards or chunks")
+        if self.hp is not None:
+            return dev.transit_expose_highpass(detrend=self.dt is not None, moments=True, model=self.want_model)
         if self.dt is not None:
             return dev.transit_expose_detrended(moments=True, model=self.want_model)
         return dev.transit_expose(moments=True, model=self.want_model)
@@ -946,7 +951,8 @@ class Transit:
         return obs.VelocityMap(job.moments, job.n_used, F)
 
     def expose(self, exposures, return_model: bool = False, devices: Optional[Sequence[int]] = None,
-               max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0, *, detrend=None):
+               max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0, *, detrend=None,
+               highpass=None):
         """Run the transit and compare it on the device with exposures taken at any phase and smeared over their
         duration: ``exposures`` is an observation.Exposures (rows, weights and factors from
         observation.exposure_taps, data and err per exposure).  R stays in device memory; per (exposure, trial) the
@@ -963,7 +969,14 @@ class Transit:
         (include/prom_hip.h, "detrended exposures on the device"); ``model`` holds the filtered model.  The filter
         is uploaded once while its content is unchanged.  The model of all trials then lies in device memory at once
         (n_exp n_trial n_pix doubles).  TypeError for anything but a Detrend, ValueError for one made for other
-        exposures, both before a device is touched.  With None nothing changes."""
+        exposures, both before a device is touched.  With None nothing changes.
+
+        ``highpass``: an observation.HighPass made for these exposures.  Every trial's model is then filtered along
+        the pixels of each order on the device, a running weighted mean subtracted or divided out, as
+        observation.high_pass filters the data (include/prom_hip.h, "high-pass filtered exposures on the device");
+        ``detrend``, if given too, runs after it, and ``model`` holds the final model.  The high-pass is uploaded once
+        while its content is unchanged, and the model of all trials lies in device memory at once.  TypeError and
+        ValueError as for ``detrend``.  With None nothing changes."""
         from . import observation as obs
         if not isinstance(exposures, obs.Exposures):
             raise TypeError("expose: exposures must be an observation.Exposures")
@@ -972,6 +985,11 @@ class Transit:
                 raise TypeError("expose: detrend must be an observation.Detrend")
             if detrend.exposures_key != exposures.key:
                 raise ValueError("expose: the Detrend was made for other exposures (another table, pixels or data)")
+        if highpass is not None:
+            if not isinstance(highpass, obs.HighPass):
+                raise TypeError("expose: highpass must be an observation.HighPass")
+            if highpass.exposures_key != exposures.key:
+                raise ValueError("expose: the HighPass was made for other exposures (another table, pixels or data)")
         n_orb = len(self.spatialGrid.constructOrbphaseAxis())
         if int(exposures.rows.max()) >= n_orb or int(exposures.rows.min()) < 0:
             raise ValueError("expose: a tap reads row %d, the transit has %d phases"
@@ -987,7 +1005,7 @@ class Transit:
                 "has %d); the moments are not additive over wavelength partials (a tap's model M = num / den needs "
                 "the sums of the whole grid before it meets the data).  Give one device and raise max_memory_gb "
                 "until the grid fits one chunk." % (len(devices), chunk, n_wav))
-        job = _ExposeJob(exposures, n_orb, return_model, detrend)
+        job = _ExposeJob(exposures, n_orb, return_model, detrend, highpass)
         self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
         model = exposures.instrument.unsort(job.model) if return_model else None
         return obs.VelocityMap(job.moments, job.n_used, exposures.factors, model=model)

@@ -276,6 +276,123 @@ class Detrend:
         self.key = ("detrend", exposures.key) + _content_fingerprint(self.U, self.W)
 
 
+MAX_HALF_WIDTH = 512   # of a high-pass' taps (the device's rolling window)
+
+
+def gaussian_taps(sigma_pix: float, truncate: float = 4.0) -> np.ndarray:
+    """Taps g[half_width + 1] of a Gaussian running mean along the pixels: g[d] = exp(-d^2 / (2 sigma_pix^2)) at
+    distance d, cut at half_width = int(truncate sigma_pix + 1/2) <= 512.  g[0] = 1; the filter normalises by the
+    weights it meets, so the taps need no norm."""
+    sigma_pix, truncate = float(sigma_pix), float(truncate)
+    if not (math.isfinite(sigma_pix) and sigma_pix > 0 and math.isfinite(truncate) and truncate >= 0):
+        raise ValueError("gaussian_taps: sigma_pix must be positive and truncate >= 0")
+    h = int(truncate * sigma_pix + 0.5)
+    if h > MAX_HALF_WIDTH:
+        raise ValueError("gaussian_taps: half width %d exceeds %d pixels" % (h, MAX_HALF_WIDTH))
+    d = np.arange(h + 1, dtype=np.float64)
+    return np.exp(-0.5 * (d / sigma_pix) ** 2)
+
+
+def box_taps(half_width: int) -> np.ndarray:
+    """Taps of a box running mean over 2 half_width + 1 pixels: ones[half_width + 1], half_width in [0, 512]."""
+    h = int(half_width)
+    if h != half_width or not 0 <= h <= MAX_HALF_WIDTH:
+        raise ValueError("box_taps: half_width must be an integer in [0, %d]" % MAX_HALF_WIDTH)
+    return np.ones(h + 1)
+
+
+def _check_taps(taps, who) -> np.ndarray:
+    g = np.array(taps, dtype=np.float64)
+    if g.ndim != 1 or not 1 <= len(g) <= MAX_HALF_WIDTH + 1:
+        raise ValueError("%s: taps must be [half_width + 1] with half_width in [0, %d]" % (who, MAX_HALF_WIDTH))
+    if not (np.all(np.isfinite(g)) and np.all(g >= 0) and g[0] > 0):
+        raise ValueError("%s: taps must be finite and >= 0, the first > 0" % who)
+    return g
+
+
+def _check_mode(mode, who) -> int:
+    if mode not in ("subtract", "divide"):
+        raise ValueError("%s: mode must be 'subtract' or 'divide'" % who)
+    return 0 if mode == "subtract" else 1
+
+
+def _order_members(orders, n_pix, who):
+    """The pixels of every order, in the caller's order, as a list of index arrays (ascending label)."""
+    if orders is None:
+        return [np.arange(n_pix)]
+    o = np.asarray(orders)
+    if o.shape != (n_pix,):
+        raise ValueError("%s: orders must hold one label per pixel" % who)
+    if not (np.issubdtype(o.dtype, np.integer) or (np.issubdtype(o.dtype, np.floating) and np.all(o == np.rint(o)))):
+        raise TypeError("%s: orders must be integer labels" % who)
+    o = o.astype(np.int64)
+    return [np.flatnonzero(o == label) for label in np.unique(o)]
+
+
+def high_pass(a, taps, orders=None, mode: str = "subtract") -> np.ndarray:
+    """The high-pass of Transit.expose(highpass=...) in numpy, over a[..., n_pix] in the caller's pixel order: what a
+    user runs on the data before sysrem.  ``orders``: an integer label per pixel (None: one order); a pixel's position
+    inside its order is its rank among that order's pixels.  At every position the running mean B over the positions
+    within half_width = len(taps) - 1 of it, weighted with taps[distance] and normalised by the weights of the
+    values that are not NaN, is subtracted from the value or divided out of it; NaN stays NaN.  The sums run in
+    ascending position and every product and sum is rounded on its own, which is the device's definition
+    (include/prom_hip.h, "high-pass filtered exposures on the device") bit for bit."""
+    g = _check_taps(taps, "high_pass")
+    m = _check_mode(mode, "high_pass")
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim < 1:
+        raise ValueError("high_pass: a must be [..., n_pix]")
+    h = len(g) - 1
+    out = np.empty_like(a)
+    for idx in _order_members(orders, a.shape[-1], "high_pass"):
+        x = a[..., idx]
+        n = len(idx)
+        num, den = np.zeros_like(x), np.zeros_like(x)
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            for d in range(-min(h, n - 1), min(h, n - 1) + 1):        # i' = i + d, ascending
+                lo, hi = max(0, -d), min(n, n - d)                    # the outputs i with 0 <= i + d < n
+                src = x[..., lo + d:hi + d]
+                ok = ~np.isnan(src)
+                num[..., lo:hi] = np.where(ok, num[..., lo:hi] + g[abs(d)] * src, num[..., lo:hi])
+                den[..., lo:hi] = np.where(ok, den[..., lo:hi] + g[abs(d)], den[..., lo:hi])
+            B = num / den
+            out[..., idx] = x - B if m == 0 else x / B
+    return out
+
+
+class HighPass:
+    """The high-pass of Transit.expose(highpass=...): every exposure's model is filtered along the pixels of each
+    order as high_pass filters data, on the device, before the SYSREM filter (if any) and the moments.  ``taps``:
+    gaussian_taps, box_taps or any [half_width + 1] weights (finite, >= 0, the first > 0, half_width <= 512);
+    ``orders``: an integer label per pixel of ``exposures`` in the caller's order (None: one order); ``mode``:
+    'subtract' or 'divide'.  The segments in the device's pixel order (``seg_first``, ``perm``) and the content key that
+    lets a device skip the upload are computed once here; the arrays are copied.  ValueError / TypeError for bad
+    arguments."""
+
+    def __init__(self, exposures: Exposures, taps, orders=None, mode: str = "subtract"):
+        from .gasProperties import _content_fingerprint
+        if not isinstance(exposures, Exposures):
+            raise TypeError("HighPass: exposures must be an observation.Exposures")
+        self.taps = np.ascontiguousarray(_check_taps(taps, "HighPass"))
+        self.half_width = len(self.taps) - 1
+        self.mode = mode
+        self.mode_id = _check_mode(mode, "HighPass")
+        ins = exposures.instrument
+        members = _order_members(orders, ins.n_pix, "HighPass")
+        self.orders = None if orders is None else np.array(orders, dtype=np.int64)
+        where = np.empty(ins.n_pix, dtype=np.int64)
+        where[ins.order] = np.arange(ins.n_pix)                 # the device's index of the caller's pixel
+        self.perm = np.ascontiguousarray(np.concatenate([where[idx] for idx in members]) if ins.n_pix
+                                         else np.zeros(0), dtype=np.int32)
+        if ins.n_pix:
+            self.seg_first = np.concatenate([[0], np.cumsum([len(idx) for idx in members])]).astype(np.int32)
+        else:
+            self.seg_first = np.zeros(2, dtype=np.int32)
+        self.n_seg = len(self.seg_first) - 1
+        self.exposures_key = exposures.key
+        self.key = ("highpass", exposures.key, self.mode_id) + _content_fingerprint(self.taps, self.perm, self.seg_first)
+
+
 def model_spectrum(num, den) -> np.ndarray:
     """M = num / den; NaN where den == 0 (no model coverage)."""
     num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
