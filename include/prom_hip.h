@@ -542,6 +542,75 @@ int32_t prom_spectrum_expose_highpass(prom_ctx* ctx, int32_t n_orb, int64_t n_wa
  * each repetition forms the unfiltered model again (untimed) before it.  PROM_E_STATE when there is no such call. */
 int32_t prom_highpass_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
 
+/* ---- per-order moments on the device ------------------------------------------------------------
+ * The likelihood of high-resolution data is defined per spectrum, that is per (exposure, echelle order): each order
+ * has its own N, its own variances of data and model and its own best-fit scale, and orders are weighted or dropped
+ * one by one.  The entries above add the moments over all pixels of an exposure; these give them per order, and the
+ * totals of the per-order statistics, without bringing the model over the bus.  All float64; the order of addition and
+ * the roundings named here are part of the definition.
+ *
+ *   resident orders      n_seg >= 1, seg_first[n_seg + 1] and perm[n_pix] (int32) under prom_highpass_set's rules:
+ *                        seg_first strictly ascending from 0 to n_pix, perm a permutation of 0 .. n_pix - 1; position i
+ *                        of order s is the device pixel perm[seg_first[s] + i] (with n_pix = 0: n_seg = 1 and {0, 0});
+ *                        keep[n_seg], uint8, 0 or 1.  The orders are independent of the resident high-pass: either
+ *                        may be there without the other, and their segments may differ
+ *   final model          the model of the exposures after the optional high-pass (highpass = 1) and the optional
+ *                        SYSREM filter (detrend = 1), each exactly as defined in its own section, in that order
+ *   record of (e, j, s)  the seven moments m0 .. m6 and n_used (int64) of the final model's row (e, j) over the
+ *                        positions of order s.  A position is used when ivar is finite and > 0, data is finite, the
+ *                        column's flag is set (with the SYSREM filter: the column is filterable; otherwise always) and
+ *                        M == M.  Its terms are iv, fl(iv M), fl(iv d), fl(fl(iv M) M), fl(fl(iv M) d), fl(fl(iv d) d)
+ *                        and fl(iv fl(fl(M - d) fl(M - d))): k_model_moments' terms and rule
+ *   order of addition    the order's positions are cut into tiles of 32 consecutive positions.  In a tile 32 terms
+ *                        t[0 .. 31] start from the used positions' values, +0 for an unused position and for the tail
+ *                        of the last tile; for m = 1, 2, 4, 8, 16 in turn every t[l] becomes fl(t[l] + t[l ^ m]) (all l
+ *                        at once), and t[0] is the tile's sum.  The tiles' sums are added in ascending tile order to a
+ *                        sum that starts at +0.  There is no chunk level (k_model_moments adds 16 tiles per chunk and
+ *                        then the chunks), so for ONE order with the identity perm and n_pix <= 512 the record is the
+ *                        lumped record of the entries above bit for bit, and otherwise it differs by rounding
+ *   independence         the eight numbers of (e, j, s) depend on the final model's row (e, j), the data and order s
+ *                        only: not on n_trial, j's position, the other orders, keep or the launcher's batches.  Two
+ *                        calls agree bit for bit; there are no floating-point atomics
+ *   totals of (e, j)     four doubles.  Order s enters when keep[s] != 0 and its n_used >= 2.  Over the entering
+ *                        orders in ascending s, each sum starting at +0: sum loglike_s, sum m6_s, sum chi2_scaled_s and
+ *                        sum n_used_s (a count held in a double).  With ratio(a, b) = NaN when b == 0, else fl(a / b):
+ *                          chi2_scaled_s = fl(m5 - ratio(fl(m4 m4), m3))
+ *                          sf = ratio(fl(m5 - ratio(fl(m2 m2), m0)), m0),  sg = ratio(fl(m3 - ratio(fl(m1 m1), m0)), m0)
+ *                          c  = ratio(fl(m4 - ratio(fl(m1 m2), m0)), m0)
+ *                          loglike_s = fl(fl(-0.5 n_used) ln(fl(fl(sf - fl(2 c)) + sg)))
+ *                        which is observation.VelocityMap's loglike and chi2_scaled on the order's record, rounding for
+ *                        rounding, so the logarithm's argument is numpy's bit for bit; ln is the device library's.  A
+ *                        NaN (or infinite) statistic of an entering order makes that total NaN (or what IEEE gives):
+ *                        nothing is hidden.  No entering order: zeros
+ *   lumped outputs       mom_out, n_used_out and model_out are what the existing entry with the same filters returns
+ *                        (prom_*_expose, _detrended, _highpass), bit for bit; without filters that holds for a model
+ *                        without NaN from R, as k_model_moments promises */
+
+/* Make the orders resident.  PROM_E_STATE without a resident exposure table; PROM_E_ARG when n_pix differs from the
+ * observation's or a rule above is broken.  The host arrays are read during the call only.  prom_expose_set, and
+ * whatever drops the exposure table, drops the orders (the calls below then fail with PROM_E_STATE). */
+int32_t prom_orders_set(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32_t* seg_first, const int32_t* perm,
+                        const uint8_t* keep);
+/* The per-order moments over the last run's R on its stream.  highpass and detrend are 0 or 1 (otherwise PROM_E_ARG);
+ * PROM_E_STATE without resident orders, with highpass = 1 without a resident high-pass and with detrend = 1 without a
+ * resident filter.  Any output may be NULL: mom_out[n_exp][n_trial][7] and n_used_out[n_exp][n_trial] (lumped),
+ * orec_mom_out[n_exp][n_trial][n_seg][7], orec_n_used_out[n_exp][n_trial][n_seg], tot_out[n_exp][n_trial][4],
+ * model_out[n_exp][n_trial][n_pix] (the final model).  n_pix = 0 gives zeros.  The model of the whole table lies in
+ * device memory at once: PROM_E_NOMEM when it does not fit (the remedy is fewer trials per call).  The records are
+ * formed in batches of whole trial groups under the PROM_VMAP_SCRATCH_MB cap.  A workgroup of k_order_moments owns one
+ * (exposure, trial group, order): n_exp n_seg >= 2^31 is PROM_E_ARG. */
+int32_t prom_transit_expose_orders(prom_ctx* ctx, int32_t highpass, int32_t detrend, double* mom_out,
+                                   int64_t* n_used_out, double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out,
+                                   double* model_out);
+/* The same for a spectrum the caller supplies (the checks of prom_spectrum_expose). */
+int32_t prom_spectrum_expose_orders(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                    int32_t highpass, int32_t detrend, double* mom_out, int64_t* n_used_out,
+                                    double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out, double* model_out);
+/* Measurement aid (tools/order_bench.py), not for callers: ms_out[0] and ms_out[1] are the mean device durations in
+ * milliseconds of k_order_moments and k_order_totals over the whole table (the first batch scaled by trial count), over
+ * n_runs repetitions on the final model the last per-order call left.  PROM_E_STATE when there is no such call. */
+int32_t prom_orders_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
+
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop
  * events on its own dispatch packet (groups of kernels: the first start to the last stop).  ms_out[k] is

@@ -144,6 +144,13 @@ SIGNATURES = {
     "prom_spectrum_expose_highpass": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _dp,
                                                   C.POINTER(C.c_int64), _dp]),
     "prom_highpass_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
+    "prom_orders_set": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_uint8)]),
+    "prom_transit_expose_orders": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, C.POINTER(C.c_int64), _dp,
+                                               C.POINTER(C.c_int64), _dp, _dp]),
+    "prom_spectrum_expose_orders": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, C.c_int32, _dp,
+                                                C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), _dp, _dp]),
+    "prom_orders_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -269,6 +276,8 @@ class Device:
         self._ex_key = None
         self._dt_key = None
         self._hp_key = None
+        self._od_key = None
+        self._od_n_seg = 0
 
     def close(self):
         if getattr(self, "h", None):
@@ -400,6 +409,7 @@ class Device:
             self._ex_shape = self._ex_key = None     # ... and the exposure table
             self._dt_key = None                      # ... with its filter
             self._hp_key = None                      # ... and its high-pass
+            self._od_key = None                      # ... and its orders
         self._n_atoms = prob.n_atoms
         self._n_pr = prob.struct.n_pr
 
@@ -480,6 +490,7 @@ class Device:
         self._ex_shape = self._ex_key = None   # ... and the exposure table
         self._dt_key = None                    # ... with its filter
         self._hp_key = None                    # ... and its high-pass
+        self._od_key = None                    # ... and its orders
         self._check(self.lib.prom_observe_set(self.h, n_pix, _d(lam), _d(sig), float(k), n_orb,
                                               _d(f) if f is not None else None,
                                               _d(data) if data is not None else None,
@@ -599,6 +610,7 @@ class Device:
         self._ex_shape = self._ex_key = None
         self._dt_key = None   # the library drops the filter with the table it was set for
         self._hp_key = None   # ... and the high-pass
+        self._od_key = None   # ... and the orders
         self._check(self.lib.prom_expose_set(self.h, n_exp, F.shape[1], n_tap, rows.ctypes.data_as(C.POINTER(C.c_int32)),
                                              _d(a), _d(F), _d(data), _d(ivar)), "prom_expose_set")
         self._ex_shape = (n_exp, F.shape[1], n_pix)
@@ -736,6 +748,70 @@ class Device:
         ms = C.c_double(0.0)
         self._check(self.lib.prom_highpass_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_highpass_kernel_ms")
         return float(ms.value)
+
+    # ---- per-order moments (prom_hip.h "per-order moments on the device") ----
+    def orders_set(self, seg_first, perm, keep=None, key=None) -> None:
+        """prom_orders_set: the orders of the resident exposure table: seg_first [n_seg + 1] and perm [n_pix] (int32;
+        position i of order s is the device pixel perm[seg_first[s] + i]) and keep [n_seg] (0 or 1; None: every order).
+        ``key``: any value the caller keeps in ``orders_key`` to skip a later upload of the same orders."""
+        seg = np.ascontiguousarray(seg_first, dtype=np.int32)
+        pm = np.ascontiguousarray(perm, dtype=np.int32)
+        if seg.ndim != 1 or len(seg) < 2 or pm.ndim != 1:
+            raise ValueError("orders_set: seg_first must be [n_seg + 1] and perm [n_pix]")
+        kp = np.ones(len(seg) - 1, dtype=np.uint8) if keep is None else np.ascontiguousarray(keep).astype(np.uint8)
+        if kp.shape != (len(seg) - 1,):
+            raise ValueError("orders_set: keep must be [n_seg]")
+        self._od_key = None
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.prom_orders_set(self.h, len(pm), len(seg) - 1, seg.ctypes.data_as(ip),
+                                             pm.ctypes.data_as(ip), kp.ctypes.data_as(C.POINTER(C.c_uint8))),
+                    "prom_orders_set")
+        self._od_key = key
+        self._od_n_seg = len(seg) - 1
+
+    @property
+    def orders_key(self):
+        """The ``key`` of the orders resident on the context (None: none, or set without a key)."""
+        return self._od_key
+
+    def _orders_outputs(self, moments: bool, records: bool, totals: bool, model: bool):
+        (mom, nu, mod), ptr = self._expose_outputs(moments, model)
+        n_exp, n_trial, _ = self._ex_shape or (0, 0, 0)
+        rm = np.zeros((n_exp, n_trial, self._od_n_seg, 7)) if records else None
+        rn = np.zeros((n_exp, n_trial, self._od_n_seg), dtype=np.int64) if records else None
+        tot = np.zeros((n_exp, n_trial, 4)) if totals else None
+        ptr = (ptr[0], ptr[1], _d(rm) if records else None, rn.ctypes.data_as(C.POINTER(C.c_int64)) if records else None,
+               _d(tot) if totals else None, ptr[2])
+        return (mom, nu, rm, rn, tot, mod), ptr
+
+    def transit_expose_orders(self, highpass: bool = False, detrend: bool = False, moments: bool = True,
+                              records: bool = True, totals: bool = True, model: bool = False):
+        """prom_transit_expose_orders over the last run's R: (moments [n_exp][n_trial][7], n_used [n_exp][n_trial],
+        order moments [n_exp][n_trial][n_seg][7], order n_used [n_exp][n_trial][n_seg], totals [n_exp][n_trial][4] =
+        (loglike, chi2, chi2_scaled, n_used) over the entering orders, final model [n_exp][n_trial][n_pix]), None for
+        what was not asked.  ``highpass`` / ``detrend``: the resident high-pass, then the resident filter, run first."""
+        out, ptr = self._orders_outputs(moments, records, totals, model)
+        self._check(self.lib.prom_transit_expose_orders(self.h, int(highpass), int(detrend), *ptr),
+                    "prom_transit_expose_orders")
+        return out
+
+    def spectrum_expose_orders(self, wav, R, highpass: bool = False, detrend: bool = False, moments: bool = True,
+                               records: bool = True, totals: bool = True, model: bool = False):
+        """prom_spectrum_expose_orders of R[n_orb][n_wav] on the ascending grid wav: transit_expose_orders' tuple."""
+        wav, R = _f64(wav), _f64(R)
+        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
+            raise ValueError("spectrum_expose_orders: R must be [n_orb][n_wav]")
+        out, ptr = self._orders_outputs(moments, records, totals, model)
+        self._check(self.lib.prom_spectrum_expose_orders(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(highpass),
+                                                         int(detrend), *ptr), "prom_spectrum_expose_orders")
+        return out
+
+    def orders_kernel_ms(self, n_runs: int = 20):
+        """prom_orders_kernel_ms: mean device durations [ms] of (k_order_moments, k_order_totals) over the whole table
+        for the last per-order call."""
+        ms = (C.c_double * 2)()
+        self._check(self.lib.prom_orders_kernel_ms(self.h, int(n_runs), ms), "prom_orders_kernel_ms")
+        return float(ms[0]), float(ms[1])
 
     # ---- stellar disk -----------------------------------------------------------------------
     def star_disk_flux(self, table_id: int, shift, clv, rho, dphi: float, drho: float, wavelength) -> np.ndarray:

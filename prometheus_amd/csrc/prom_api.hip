@@ -15,6 +15,7 @@
 #include "vmap_index.h"
 #include "detrend_index.h"
 #include "highpass_index.h"
+#include "order_index.h"
 
 using prom::DevBuf;
 using prom::Error;
@@ -2101,6 +2102,7 @@ int32_t prom_expose_set(prom_ctx* ctx, int32_t n_exp, int32_t n_trial, int32_t n
     ex.set = false;
     ex.dt_set = ex.dt_ran = false;   // a filter belongs to the table it was set for
     ex.hp_set = ex.hp_ran = false;   // ... and so does a high-pass
+    ex.od_set = ex.od_ran = false;   // ... and the orders of the per-order moments
     ex.last_wav = ex.last_R = nullptr;
     PROM_REQUIRE(n_exp >= 1 && n_exp <= 65535 && n_trial >= 1 && n_trial <= (1 << 24) && n_tap >= 1 &&
                      n_tap <= (1 << 16) && row && a && F,
@@ -2178,7 +2180,7 @@ static void expose_on(prom_ctx* ctx, hipStream_t st, const double* wav, const do
   ex.last_wav = wav;
   ex.last_R = R;
   ex.last_n_wav = (int32_t)n_wav;
-  ex.dt_ran = ex.hp_ran = false;
+  ex.dt_ran = ex.hp_ran = ex.od_ran = false;
   if (mom_out) download(mom_out, ex.mom, 7 * n, st);
   if (n_used_out) download(n_used_out, ex.n_used, n, st);
   if (model_out) download(model_out, ex.model, nm, st);
@@ -2329,7 +2331,7 @@ static void detrend_on(prom_ctx* ctx, hipStream_t st, const double* wav, const d
   ex.last_R = R;
   ex.last_n_wav = (int32_t)n_wav;
   ex.dt_ran = true;
-  ex.hp_ran = false;
+  ex.hp_ran = ex.od_ran = false;
   if (mom_out) download(mom_out, ex.mom, 7 * n, st);
   if (n_used_out) download(n_used_out, ex.n_used, n, st);
   if (model_out) download(model_out, ex.model, nm, st);
@@ -2492,7 +2494,7 @@ static void highpass_on(prom_ctx* ctx, hipStream_t st, const double* wav, const 
   ex.last_wav = wav;
   ex.last_R = R;
   ex.last_n_wav = (int32_t)n_wav;
-  ex.dt_ran = false;
+  ex.dt_ran = ex.od_ran = false;
   ex.hp_ran = true;
   ex.hp_detrend = detrend;
   if (mom_out) download(mom_out, ex.mom, 7 * n, st);
@@ -2562,6 +2564,219 @@ int32_t prom_highpass_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
       sum += ms;
     }
     ms_out[0] = sum / n_runs;
+  });
+}
+
+// ------------------------------------------------------------------------------ per-order moments
+int32_t prom_orders_set(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32_t* seg_first, const int32_t* perm,
+                        const uint8_t* keep) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    ex.od_set = ex.od_ran = false;
+    if (!ex.set || !ctx->obs.set || ctx->obs.n_orb != ex.n_orb)
+      throw Error(PROM_E_STATE, "prom_orders_set: no exposure table on the context (prom_expose_set)");
+    PROM_REQUIRE(n_pix == ctx->obs.n_pix, "prom_orders_set: n_pix differs from the observation's");
+    PROM_REQUIRE(n_seg >= 1 && seg_first && keep && (n_pix == 0 || perm), "prom_orders_set: orders missing");
+    if (n_pix == 0) {   // no pixel: no order can hold one; the calls give zeros
+      PROM_REQUIRE(n_seg == 1 && seg_first[0] == 0 && seg_first[1] == 0,
+                   "prom_orders_set: without pixels seg_first must be {0, 0}");
+    } else {
+      PROM_REQUIRE(n_seg <= n_pix && seg_first[0] == 0 && seg_first[n_seg] == n_pix,
+                   "prom_orders_set: seg_first must run from 0 to n_pix");
+      for (int32_t i = 0; i < n_seg; ++i)
+        PROM_REQUIRE(seg_first[i + 1] > seg_first[i], "prom_orders_set: seg_first must be strictly ascending");
+      std::vector<char> seen((size_t)n_pix, 0);
+      for (int32_t i = 0; i < n_pix; ++i) {
+        PROM_REQUIRE(perm[i] >= 0 && perm[i] < n_pix && !seen[(size_t)perm[i]],
+                     "prom_orders_set: perm must be a permutation of 0 .. n_pix - 1");
+        seen[(size_t)perm[i]] = 1;
+      }
+    }
+    for (int32_t i = 0; i < n_seg; ++i) PROM_REQUIRE(keep[i] <= 1, "prom_orders_set: keep must be 0 or 1");
+    const hipStream_t st = ctx->stream;
+    upload(ex.od_seg, seg_first, (int64_t)n_seg + 1, st);
+    upload(ex.od_perm, perm, (int64_t)n_pix, st);
+    upload(ex.od_keep, keep, (int64_t)n_seg, st);
+    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
+    ex.od_n_seg = n_seg;
+    ex.od_set = true;
+  });
+}
+
+// k_order_moments + k_order_totals over the final model in ex.model, in batches of whole trial groups under the scratch
+// cap (one group at least); a batch's records go to the caller's arrays when they are wanted (ev: events around the two
+// kernels of the first batch)
+static void orders_launch(prom_ctx* ctx, hipStream_t st, double* orec_mom_out, int64_t* orec_n_used_out,
+                          hipEvent_t* ev) {
+  prom::ExDev& ex = ctx->ex;
+  const int32_t n_pix = ctx->obs.n_pix, n_seg = ex.od_n_seg, n_groups = prom::od_groups(ex.n_trial);
+  const int32_t bg = prom::od_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, n_seg, n_groups);
+  const int32_t nb_max = std::min(bg * prom::kOdTrials, ex.n_trial);
+  ex.od_rec.ensure(sizeof(double) * (size_t)prom::od_record_doubles(ex.n_exp, nb_max, n_seg));
+  ex.od_tot.ensure(sizeof(double) * (size_t)prom::kOdTotals * ex.n_exp * ex.n_trial);
+  static const bool debug = std::getenv("PROM_DEBUG") != nullptr;
+  if (debug)
+    std::fprintf(stderr, "prom: per-order moments: %d trials in %d groups, %d batches of up to %d groups, %d orders\n",
+                 ex.n_trial, n_groups, (n_groups + bg - 1) / bg, bg, n_seg);
+  const bool want = orec_mom_out || orec_n_used_out;
+  std::vector<double> host;
+  if (want) host.resize((size_t)prom::od_record_doubles(ex.n_exp, nb_max, n_seg));
+  for (int32_t g = 0; g < n_groups; g += bg) {
+    const int32_t j_first = prom::od_group_first(g), nb = std::min(nb_max, ex.n_trial - j_first);
+    prom::launch_order_moments(st, ex.model.as<double>(), ex.flag.as<uint8_t>(), ex.data.as<double>(),
+                               ex.ivar.as<double>(), ex.od_seg.as<int32_t>(), ex.od_perm.as<int32_t>(), n_pix, ex.n_exp,
+                               ex.n_trial, j_first, nb, n_seg, ex.od_rec.as<double>(), ev && g == 0 ? ev[0] : nullptr,
+                               ev && g == 0 ? ev[1] : nullptr);
+    prom::launch_order_totals(st, ex.od_rec.as<double>(), ex.od_keep.as<uint8_t>(), ex.n_exp, ex.n_trial, j_first, nb,
+                              n_seg, ex.od_tot.as<double>(), ev && g == 0 ? ev[2] : nullptr,
+                              ev && g == 0 ? ev[3] : nullptr);
+    if (!want) continue;
+    download(host.data(), ex.od_rec, prom::od_record_doubles(ex.n_exp, nb, n_seg), st);
+    PROM_HIP(hipStreamSynchronize(st));   // (the next batch writes the same buffer)
+    for (int32_t e = 0; e < ex.n_exp; ++e)
+      for (int32_t jb = 0; jb < nb; ++jb)
+        for (int32_t s = 0; s < n_seg; ++s) {
+          const double* rec = host.data() + prom::od_record(e, jb, s, nb, n_seg);
+          const int64_t to = ((int64_t)e * ex.n_trial + j_first + jb) * n_seg + s;
+          if (orec_mom_out) std::copy(rec, rec + 7, orec_mom_out + 7 * to);
+          if (orec_n_used_out) std::memcpy(orec_n_used_out + to, rec + 7, sizeof(int64_t));
+        }
+  }
+}
+
+// the shared tail of the two per-order calls, on stream st
+static void orders_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav,
+                      int32_t highpass, int32_t detrend, double* mom_out, int64_t* n_used_out, double* orec_mom_out,
+                      int64_t* orec_n_used_out, double* tot_out, double* model_out) {
+  prom::ExDev& ex = ctx->ex;
+  const int32_t n_pix = ctx->obs.n_pix, n_seg = ex.od_n_seg;
+  const int64_t n = (int64_t)ex.n_exp * ex.n_trial;
+  ex.od_ran = false;
+  if (n_pix == 0) {   // no pixel: every moment, record and total 0 and no model value
+    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
+    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
+    if (orec_mom_out) std::fill(orec_mom_out, orec_mom_out + 7 * n * n_seg, 0.0);
+    if (orec_n_used_out) std::fill(orec_n_used_out, orec_n_used_out + n * n_seg, (int64_t)0);
+    if (tot_out) std::fill(tot_out, tot_out + prom::kOdTotals * n, 0.0);
+    return;
+  }
+  const bool want_orders = orec_mom_out || orec_n_used_out || tot_out;
+  if (!mom_out && !n_used_out && !want_orders && !model_out) return;
+  // (before anything is launched)
+  if (prom::od_workgroups(ex.n_exp, 1, n_seg) > (((int64_t)1 << 31) - 1))
+    throw Error(PROM_E_ARG, "k_order_moments: n_exp n_seg too large for one launch");
+  if (highpass && prom::hp_workgroups(n, ex.hp_n_seg) > (((int64_t)1 << 31) - 1))
+    throw Error(PROM_E_ARG, "k_highpass: n_exp n_trial n_seg too large for one launch");
+  const double nan = std::nan("");
+  const int64_t nm = n * n_pix;
+  ex.q.ensure(sizeof(double) * (size_t)n_wav);
+  try {   // the whole table's model is resident at once: it is not batched
+    ex.model.ensure(sizeof(double) * (size_t)nm);
+  } catch (const Error& err) {
+    throw Error(err.code, std::string(err.what()) + ": the per-order moments keep the model of all " +
+                              std::to_string(ex.n_trial) + " trials in device memory; give fewer trials per call");
+  }
+  ex.flag.ensure((size_t)ex.n_trial * n_pix);
+  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
+  // the final model: k_expose without moments, then the filters asked for, as highpass_model / detrend_model run them
+  expose_launch(ctx, st, wav, R, (int32_t)n_wav, false, ex.model.as<double>(), nullptr, nullptr);
+  if (highpass)
+    prom::launch_highpass(st, ex.model.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(),
+                          ex.hp_g.as<double>(), ex.hp_half, ex.hp_den, ex.hp_mode, n, ex.hp_n_seg, n_pix, nullptr,
+                          nullptr);
+  if (detrend)
+    prom::launch_detrend(st, ex.model.as<double>(), ex.U.as<double>(), ex.W.as<double>(), ex.flag.as<uint8_t>(),
+                         ex.n_exp, ex.n_comp, ex.n_trial, n_pix, nullptr, nullptr);
+  else
+    PROM_HIP(hipMemsetAsync(ex.flag.as<uint8_t>(), 1, (size_t)ex.n_trial * n_pix, st));
+  if (mom_out || n_used_out) moments_launch(ctx, st, nullptr, nullptr);
+  ex.last_wav = wav;
+  ex.last_R = R;
+  ex.last_n_wav = (int32_t)n_wav;
+  ex.dt_ran = ex.hp_ran = false;
+  ex.od_ran = true;
+  if (want_orders) orders_launch(ctx, st, orec_mom_out, orec_n_used_out, nullptr);
+  if (mom_out) download(mom_out, ex.mom, 7 * n, st);
+  if (n_used_out) download(n_used_out, ex.n_used, n, st);
+  if (tot_out) download(tot_out, ex.od_tot, prom::kOdTotals * n, st);
+  if (model_out) download(model_out, ex.model, nm, st);
+  PROM_HIP(hipStreamSynchronize(st));
+}
+
+static void orders_check(prom_ctx* ctx, const char* who, int32_t highpass, int32_t detrend) {
+  expose_check(ctx, who);
+  if (!ctx->ex.od_set)
+    throw Error(PROM_E_STATE, std::string(who) + ": no orders on the context (prom_orders_set; a later "
+                                                 "prom_expose_set, or whatever drops the exposure table, drops them)");
+  if (highpass != 0 && highpass != 1) throw Error(PROM_E_ARG, std::string(who) + ": highpass must be 0 or 1");
+  if (detrend != 0 && detrend != 1) throw Error(PROM_E_ARG, std::string(who) + ": detrend must be 0 or 1");
+  if (highpass && !ctx->ex.hp_set)
+    throw Error(PROM_E_STATE, std::string(who) + ": highpass = 1 without a high-pass on the context (prom_highpass_set)");
+  if (detrend && !ctx->ex.dt_set)
+    throw Error(PROM_E_STATE, std::string(who) + ": detrend = 1 without a filter on the context (prom_detrend_set)");
+}
+
+int32_t prom_transit_expose_orders(prom_ctx* ctx, int32_t highpass, int32_t detrend, double* mom_out,
+                                   int64_t* n_used_out, double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out,
+                                   double* model_out) {
+  return guarded(ctx, [&] {
+    prom::TransitDev& tr = ctx->tr;
+    orders_check(ctx, "prom_transit_expose_orders", highpass, detrend);
+    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose_orders: no completed run");
+    if (ctx->ex.n_orb != tr.n_orb)
+      throw Error(PROM_E_STATE, "prom_transit_expose_orders: the exposure table has another n_orb");
+    orders_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, highpass,
+              detrend, mom_out, n_used_out, orec_mom_out, orec_n_used_out, tot_out, model_out);
+  });
+}
+
+int32_t prom_spectrum_expose_orders(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                    int32_t highpass, int32_t detrend, double* mom_out, int64_t* n_used_out,
+                                    double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out,
+                                    double* model_out) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    orders_check(ctx, "prom_spectrum_expose_orders", highpass, detrend);
+    PROM_REQUIRE(n_orb == ex.n_orb, "prom_spectrum_expose_orders: n_orb differs from the observation's");
+    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_expose_orders: bad spectrum");
+    for (int64_t w = 0; w < n_wav; ++w)
+      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
+                   "prom_spectrum_expose_orders: wavelengths must be finite and ascending");
+    const hipStream_t st = ctx->stream;
+    ex.last_wav = ex.last_R = nullptr;   // (the uploads may move the buffers the last call read)
+    ex.od_ran = false;
+    upload(ex.wav, wav, n_wav, st);
+    upload(ex.R, R, (int64_t)n_orb * n_wav, st);
+    orders_on(ctx, st, ex.wav.as<double>(), ex.R.as<double>(), n_wav, highpass, detrend, mom_out, n_used_out,
+              orec_mom_out, orec_n_used_out, tot_out, model_out);
+  });
+}
+
+int32_t prom_orders_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_orders_kernel_ms: bad arguments");
+    if (!ex.set || !ex.od_set || !ex.od_ran || !ctx->obs.set || ctx->obs.n_pix == 0)
+      throw Error(PROM_E_STATE, "prom_orders_kernel_ms: no per-order call to repeat");
+    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
+    const hipStream_t st = ctx->stream;
+    // the two kernels read the final model and the flags the last call left; the first batch, scaled to the table by
+    // trial count
+    const int32_t n_groups = prom::od_groups(ex.n_trial);
+    const int32_t bg = prom::od_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, ex.od_n_seg, n_groups);
+    const double scale = (double)ex.n_trial / (double)std::min(bg * prom::kOdTrials, ex.n_trial);
+    double sum[2] = {0.0, 0.0};
+    for (int32_t r = 0; r < n_runs; ++r) {
+      orders_launch(ctx, st, nullptr, nullptr, ctx->ev);
+      PROM_HIP(hipStreamSynchronize(st));
+      float ms = 0.0f;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      sum[0] += ms;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+      sum[1] += ms;
+    }
+    ms_out[0] = scale * sum[0] / n_runs;
+    ms_out[1] = scale * sum[1] / n_runs;
   });
 }
 

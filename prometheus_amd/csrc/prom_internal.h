@@ -469,6 +469,13 @@ struct ExDev {
   DevBuf hp_seg, hp_perm, hp_g;           // seg_first[n_seg + 1], perm[n_pix] (int32), g[half_width + 1]
   bool hp_ran = false;                    // the last call on last_wav / last_R was a high-pass one ...
   int32_t hp_detrend = 0;                 // ... with this `detrend`
+  // The orders of the per-order moments (prom_orders_set): independent of the high-pass, they live while the table
+  // they were set for does, and prom_expose_set clears od_set.
+  bool od_set = false;
+  int32_t od_n_seg = 0;
+  DevBuf od_seg, od_perm, od_keep;        // seg_first[n_seg + 1], perm[n_pix] (int32), keep[n_seg] (bytes)
+  DevBuf od_rec, od_tot;                  // a batch's records [n_exp][nb][n_seg][8], the totals [n_exp][n_trial][4]
+  bool od_ran = false;                    // the last call was a per-order one: its final model and flags are resident
 };
 
 }  // namespace prom
@@ -607,6 +614,15 @@ void launch_model_moments(hipStream_t s, const double* model, const uint8_t* fla
 void launch_highpass(hipStream_t s, double* model, const int32_t* seg_first, const int32_t* perm, const double* g,
                      int32_t half_width, double den_full, int32_t mode, int64_t n_rows, int32_t n_seg, int32_t n_pix,
                      hipEvent_t ev0, hipEvent_t ev1);
+// per-order moments (prom_orders.hip): the records orec[n_exp][nb][n_seg][8] of the trials [j_first, j_first + nb) of
+// the model that lies in memory, over the orders seg_first[n_seg + 1] / perm[n_pix]; then the totals
+// tot[n_exp][n_trial][4] of the same trials from the records and keep[n_seg]
+void launch_order_moments(hipStream_t s, const double* model, const uint8_t* flag, const double* data,
+                          const double* ivar, const int32_t* seg_first, const int32_t* perm, int32_t n_pix,
+                          int32_t n_exp, int32_t n_trial, int32_t j_first, int32_t nb, int32_t n_seg, double* orec,
+                          hipEvent_t ev0, hipEvent_t ev1);
+void launch_order_totals(hipStream_t s, const double* orec, const uint8_t* keep, int32_t n_exp, int32_t n_trial,
+                         int32_t j_first, int32_t nb, int32_t n_seg, double* tot, hipEvent_t ev0, hipEvent_t ev1);
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

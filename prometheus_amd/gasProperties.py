@@ -652,14 +652,17 @@ class _ExposeJob:
     """One Transit.expose call inside _integrate: the pixels and the exposure table go to the device once each while
     their content keys are unchanged, then the exposures run over the (one) chunk's R."""
 
-    def __init__(self, exposures, n_orb, want_model, detrend=None, highpass=None):
+    def __init__(self, exposures, n_orb, want_model, detrend=None, highpass=None, orders=None, order_records=True):
         self.ex = exposures
         self.obs = _ObserveJob(exposures.pixels(n_orb), False)
         self.want_model = want_model
         self.dt = detrend
         self.hp = highpass
+        self.od = orders
+        self.od_records = order_records
         self.whole = False
         self.moments = self.n_used = self.model = None
+        self.order_moments = self.order_n_used = self.order_totals = None
 
     def upload(self, dev) -> None:
         self.obs.upload(dev)
@@ -669,10 +672,17 @@ class _ExposeJob:
             dev.detrend_set(self.dt.U, self.dt.W, key=self.dt.key)
         if self.hp is not None and dev.highpass_key != self.hp.key:   # (likewise)
             dev.highpass_set(self.hp.seg_first, self.hp.perm, self.hp.taps, self.hp.mode_id, key=self.hp.key)
+        if self.od is not None and dev.orders_key != self.od.key:   # (likewise)
+            dev.orders_set(self.od.seg_first, self.od.perm, self.od.keep, key=self.od.key)
 
     def run(self, dev, wavelength, a: int, b: int):
         if not self.whole:   # (expose refuses such a run before it starts)
             raise RuntimeError("expose: the run was split into wavelength shards or chunks")
+        if self.od is not None:
+            mom, nu, self.order_moments, self.order_n_used, self.order_totals, model = dev.transit_expose_orders(
+                highpass=self.hp is not None, detrend=self.dt is not None, moments=True, records=self.od_records,
+                totals=True, model=self.want_model)
+            return mom, nu, model
         if self.hp is not None:
             return dev.transit_expose_highpass(detrend=self.dt is not None, moments=True, model=self.want_model)
         if self.dt is not None:
@@ -952,7 +962,7 @@ class Transit:
 
     def expose(self, exposures, return_model: bool = False, devices: Optional[Sequence[int]] = None,
                max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0, *, detrend=None,
-               highpass=None):
+               highpass=None, orders=None, order_records: bool = True):
         """Run the transit and compare it on the device with exposures taken at any phase and smeared over their
         duration: ``exposures`` is an observation.Exposures (rows, weights and factors from
         observation.exposure_taps, data and err per exposure).  R stays in device memory; per (exposure, trial) the
@@ -976,7 +986,16 @@ class Transit:
         observation.high_pass filters the data (include/prom_hip.h, "high-pass filtered exposures on the device");
         ``detrend``, if given too, runs after it, and ``model`` holds the final model.  The high-pass is uploaded once
         while its content is unchanged, and the model of all trials lies in device memory at once.  TypeError and
-        ValueError as for ``detrend``.  With None nothing changes."""
+        ValueError as for ``detrend``.  With None nothing changes.
+
+        ``orders``: an observation.Orders made for these exposures.  The moments of the final model (after
+        ``highpass`` and ``detrend``, if given) are then also formed per echelle order on the device
+        (include/prom_hip.h, "per-order moments on the device"), and the returned map carries ``by_order`` (an
+        observation.OrderMap [n_exp][n_trial][n_seg]; None with ``order_records=False``) and ``order_totals``
+        (observation.OrderTotals: loglike, chi2, chi2_scaled and n_used over the kept orders with two used pixels at
+        least, each [n_exp][n_trial], formed on the device: 32 bytes per (exposure, trial) cross the bus).  The orders
+        are uploaded once while their content is unchanged, and the model of all trials lies in device memory at once.
+        TypeError and ValueError as for ``detrend``.  With None nothing changes."""
         from . import observation as obs
         if not isinstance(exposures, obs.Exposures):
             raise TypeError("expose: exposures must be an observation.Exposures")
@@ -990,6 +1009,11 @@ class Transit:
                 raise TypeError("expose: highpass must be an observation.HighPass")
             if highpass.exposures_key != exposures.key:
                 raise ValueError("expose: the HighPass was made for other exposures (another table, pixels or data)")
+        if orders is not None:
+            if not isinstance(orders, obs.Orders):
+                raise TypeError("expose: orders must be an observation.Orders")
+            if orders.exposures_key != exposures.key:
+                raise ValueError("expose: the Orders were made for other exposures (another table, pixels or data)")
         n_orb = len(self.spatialGrid.constructOrbphaseAxis())
         if int(exposures.rows.max()) >= n_orb or int(exposures.rows.min()) < 0:
             raise ValueError("expose: a tap reads row %d, the transit has %d phases"
@@ -1005,10 +1029,16 @@ class Transit:
                 "has %d); the moments are not additive over wavelength partials (a tap's model M = num / den needs "
                 "the sums of the whole grid before it meets the data).  Give one device and raise max_memory_gb "
                 "until the grid fits one chunk." % (len(devices), chunk, n_wav))
-        job = _ExposeJob(exposures, n_orb, return_model, detrend, highpass)
+        job = _ExposeJob(exposures, n_orb, return_model, detrend, highpass, orders, order_records)
         self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
         model = exposures.instrument.unsort(job.model) if return_model else None
-        return obs.VelocityMap(job.moments, job.n_used, exposures.factors, model=model)
+        vm = obs.VelocityMap(job.moments, job.n_used, exposures.factors, model=model)
+        if orders is not None:
+            vm.by_order = None
+            if order_records:
+                vm.by_order = obs.OrderMap(job.order_moments, job.order_n_used, orders.labels, orders.keep)
+            vm.order_totals = obs.OrderTotals(job.order_totals)
+        return vm
 
     def _wavelength_chunk(self, max_memory_gb, n_orb: int) -> int:
         """Wavelengths per device step under ``max_memory_gb``."""

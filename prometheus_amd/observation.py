@@ -393,6 +393,47 @@ class HighPass:
         self.key = ("highpass", exposures.key, self.mode_id) + _content_fingerprint(self.taps, self.perm, self.seg_first)
 
 
+class Orders:
+    """The echelle orders of Transit.expose(orders=...): the moments of every (exposure, trial) are then also formed per
+    order on the device (include/prom_hip.h, "per-order moments on the device").  ``orders``: an integer label per
+    pixel of ``exposures`` in the caller's order, as for HighPass (None: one order); ``keep``: a bool per label in
+    ascending label order, whether the order enters the totals (None: every order).  ``labels`` holds the labels in
+    ascending order; the segments in the device's pixel order (``seg_first``, ``perm``) and the content key that lets
+    a device skip the upload are computed once here; the arrays are copied.  The object is independent of a HighPass:
+    either may be used without the other.  ValueError / TypeError for bad arguments."""
+
+    def __init__(self, exposures: Exposures, orders, keep=None):
+        from .gasProperties import _content_fingerprint
+        if not isinstance(exposures, Exposures):
+            raise TypeError("Orders: exposures must be an observation.Exposures")
+        ins = exposures.instrument
+        members = _order_members(orders, ins.n_pix, "Orders")
+        self.orders = None if orders is None else np.array(orders, dtype=np.int64)
+        self.labels = np.zeros(1, dtype=np.int64) if orders is None else np.unique(self.orders)
+        where = np.empty(ins.n_pix, dtype=np.int64)
+        where[ins.order] = np.arange(ins.n_pix)                 # the device's index of the caller's pixel
+        self.perm = np.ascontiguousarray(np.concatenate([where[idx] for idx in members]) if ins.n_pix
+                                         else np.zeros(0), dtype=np.int32)
+        if ins.n_pix:
+            self.seg_first = np.concatenate([[0], np.cumsum([len(idx) for idx in members])]).astype(np.int32)
+        else:
+            self.seg_first = np.zeros(2, dtype=np.int32)
+            self.labels = np.zeros(1, dtype=np.int64)
+        self.n_seg = len(self.seg_first) - 1
+        if keep is None:
+            self.keep = np.ones(self.n_seg, dtype=bool)
+        else:
+            k = np.asarray(keep)
+            if k.shape != (self.n_seg,):
+                raise ValueError("Orders: keep must hold one entry per order label (%d)" % self.n_seg)
+            if not (k.dtype == bool or (np.issubdtype(k.dtype, np.integer) and np.all((k == 0) | (k == 1)))):
+                raise TypeError("Orders: keep must be bool (or 0 / 1)")
+            self.keep = k.astype(bool)
+        self.exposures_key = exposures.key
+        self.key = ("orders", exposures.key) + _content_fingerprint(self.perm, self.seg_first,
+                                                                    self.keep.astype(np.uint8))
+
+
 def model_spectrum(num, den) -> np.ndarray:
     """M = num / den; NaN where den == 0 (no model coverage)."""
     num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
@@ -521,24 +562,11 @@ def _ratio(a, b):
         return np.where(b == 0.0, np.nan, a / np.where(b == 0.0, 1.0, b))
 
 
-class VelocityMap:
-    """Result of Transit.velocity_map: ``moments`` [n_orb][n_trial][7] and ``n_used`` [n_orb][n_trial] of the model in
-    every trial frame against the data (include/prom_hip.h, "velocity maps on the device"; m0 = sum iv,
-    m1 = sum iv M, m2 = sum iv d, m3 = sum iv M^2, m4 = sum iv M d, m5 = sum iv d^2, m6 = sum iv (M - d)^2 over the
-    used pixels) and the table ``factors`` they belong to.  The statistics are per (phase, trial), NaN where their
-    denominator is 0.  From Transit.expose the first axis counts exposures, ``factors`` is the exposures'
-    [n_exp][n_trial][n_tap] table and ``model`` [n_exp][n_trial][n_pix] holds the exposures' model spectra in the
-    caller's pixel order when they were asked for (None otherwise, and from velocity_map)."""
+class _MomentStats:
+    """The statistics of seven moments ``moments`` [..., 7] and ``n_used`` [...]: shared by VelocityMap (per phase or
+    exposure and trial) and OrderMap (per exposure, trial and order).  NaN where a denominator is 0."""
 
     STATS = ("chi2", "chi2_scaled", "scale", "ccf", "loglike")
-
-    def __init__(self, moments, n_used, factors, model=None):
-        self.model = model
-        self.moments = np.asarray(moments, dtype=np.float64)
-        self.n_used = np.asarray(n_used, dtype=np.int64)
-        self.factors = np.asarray(factors, dtype=np.float64)
-        if self.moments.ndim != 3 or self.moments.shape[2] != 7 or self.n_used.shape != self.moments.shape[:2]:
-            raise ValueError("VelocityMap: moments must be [n_orb][n_trial][7] and n_used [n_orb][n_trial]")
 
     def _m(self, i):
         return self.moments[..., i]
@@ -577,20 +605,94 @@ class VelocityMap:
     def _stat(self, stat):
         if isinstance(stat, str):
             if stat not in self.STATS:
-                raise ValueError("VelocityMap: unknown statistic %r (one of %s)" % (stat, ", ".join(self.STATS)))
+                raise ValueError("%s: unknown statistic %r (one of %s)" % (type(self).__name__, stat,
+                                                                           ", ".join(self.STATS)))
             return getattr(self, stat)
         return np.asarray(stat, dtype=np.float64)
-
-    def total(self, stat="chi2"):
-        """The statistic (a name or an array [n_orb][n_trial]) summed over the phases: [n_trial]."""
-        return self._stat(stat).sum(axis=0)
 
     def grid(self, stat, n_kp: int, n_vsys: int):
         """A Kp-major statistic ([..., nKp * nVsys], e.g. over a kp_vsys_factors table) as [..., nKp, nVsys]."""
         s = self._stat(stat)
         if s.shape[-1] != n_kp * n_vsys:
-            raise ValueError("VelocityMap.grid: %d trials are no %d x %d grid" % (s.shape[-1], n_kp, n_vsys))
+            raise ValueError("%s.grid: %d trials are no %d x %d grid" % (type(self).__name__, s.shape[-1], n_kp, n_vsys))
         return s.reshape(s.shape[:-1] + (n_kp, n_vsys))
+
+
+class VelocityMap(_MomentStats):
+    """Result of Transit.velocity_map: ``moments`` [n_orb][n_trial][7] and ``n_used`` [n_orb][n_trial] of the model in
+    every trial frame against the data (include/prom_hip.h, "velocity maps on the device"; m0 = sum iv,
+    m1 = sum iv M, m2 = sum iv d, m3 = sum iv M^2, m4 = sum iv M d, m5 = sum iv d^2, m6 = sum iv (M - d)^2 over the
+    used pixels) and the table ``factors`` they belong to.  The statistics are per (phase, trial), NaN where their
+    denominator is 0.  From Transit.expose the first axis counts exposures, ``factors`` is the exposures'
+    [n_exp][n_trial][n_tap] table and ``model`` [n_exp][n_trial][n_pix] holds the exposures' model spectra in the
+    caller's pixel order when they were asked for (None otherwise, and from velocity_map).  From
+    Transit.expose(orders=...) it also carries ``by_order`` (an OrderMap, or None when the records were not asked for)
+    and ``order_totals`` (OrderTotals, formed on the device)."""
+
+    def __init__(self, moments, n_used, factors, model=None):
+        self.model = model
+        self.moments = np.asarray(moments, dtype=np.float64)
+        self.n_used = np.asarray(n_used, dtype=np.int64)
+        self.factors = np.asarray(factors, dtype=np.float64)
+        if self.moments.ndim != 3 or self.moments.shape[2] != 7 or self.n_used.shape != self.moments.shape[:2]:
+            raise ValueError("VelocityMap: moments must be [n_orb][n_trial][7] and n_used [n_orb][n_trial]")
+
+    def total(self, stat="chi2"):
+        """The statistic (a name or an array [n_orb][n_trial]) summed over the phases: [n_trial]."""
+        return self._stat(stat).sum(axis=0)
+
+
+class OrderMap(_MomentStats):
+    """The per-order moments of Transit.expose(orders=...): ``moments`` [n_exp][n_trial][n_seg][7] and ``n_used``
+    [n_exp][n_trial][n_seg] of the final model against the data over each order's pixels (include/prom_hip.h,
+    "per-order moments on the device"), the orders' ``labels`` [n_seg] in ascending order and ``keep`` [n_seg].  The
+    statistics are VelocityMap's, per (exposure, trial, order)."""
+
+    def __init__(self, moments, n_used, labels, keep):
+        self.moments = np.asarray(moments, dtype=np.float64)
+        self.n_used = np.asarray(n_used, dtype=np.int64)
+        self.labels = np.asarray(labels, dtype=np.int64)
+        self.keep = np.asarray(keep, dtype=bool)
+        if self.moments.ndim != 4 or self.moments.shape[3] != 7 or self.n_used.shape != self.moments.shape[:3]:
+            raise ValueError("OrderMap: moments must be [n_exp][n_trial][n_seg][7] and n_used [n_exp][n_trial][n_seg]")
+        if self.labels.shape != self.moments.shape[2:3] or self.keep.shape != self.labels.shape:
+            raise ValueError("OrderMap: labels and keep must be [n_seg]")
+
+    def enters(self, keep=None):
+        """Whether (exposure, trial, order) enters a total: the order is kept (``keep`` [n_seg], None: the map's own)
+        and has two used pixels at least."""
+        k = self.keep if keep is None else np.asarray(keep, dtype=bool)
+        if k.shape != self.keep.shape:
+            raise ValueError("OrderMap: keep must be [n_seg]")
+        return k[None, None, :] & (self.n_used >= 2)
+
+    def total(self, stat="chi2", keep=None):
+        """The statistic (a name or an array [n_exp][n_trial][n_seg]) summed over the exposures and the entering
+        orders: [n_trial].  A NaN statistic of an entering order makes the total NaN."""
+        return np.where(self.enters(keep), self._stat(stat), 0.0).sum(axis=(0, 2))
+
+    def grid(self, stat, n_kp: int, n_vsys: int):
+        """A Kp-major statistic as a grid: [n_exp][nKp * nVsys][n_seg] (a name, or an array of that shape) becomes
+        [n_exp][nKp][nVsys][n_seg]; any other array, a total [nKp * nVsys] say, is taken along its last axis as in
+        VelocityMap.grid."""
+        s = self._stat(stat)
+        if s.shape != self.n_used.shape:
+            return super().grid(s, n_kp, n_vsys)
+        if s.shape[1] != n_kp * n_vsys:
+            raise ValueError("OrderMap.grid: %d trials are no %d x %d grid" % (s.shape[1], n_kp, n_vsys))
+        return s.reshape(s.shape[:1] + (n_kp, n_vsys) + s.shape[2:])
+
+
+class OrderTotals:
+    """The totals of Transit.expose(orders=...) as the device formed them, each [n_exp][n_trial] over the entering
+    orders (kept, n_used >= 2) in ascending label: ``loglike``, ``chi2``, ``chi2_scaled`` and ``n_used`` (int64)."""
+
+    def __init__(self, totals):
+        t = np.asarray(totals, dtype=np.float64)
+        if t.ndim != 3 or t.shape[2] != 4:
+            raise ValueError("OrderTotals: totals must be [n_exp][n_trial][4]")
+        self.loglike, self.chi2, self.chi2_scaled = t[..., 0], t[..., 1], t[..., 2]
+        self.n_used = t[..., 3].astype(np.int64)
 
 
 class Observed:
