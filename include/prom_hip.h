@@ -611,6 +611,66 @@ int32_t prom_spectrum_expose_orders(prom_ctx* ctx, int32_t n_orb, int64_t n_wav,
  * n_runs repetitions on the final model the last per-order call left.  PROM_E_STATE when there is no such call. */
 int32_t prom_orders_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
 
+/* ---- broadened spectra on the device ------------------------------------------------------------
+ * The planet's own velocity field broadens and shifts every line before the instrument sees it: the rigid rotation of
+ * a tidally locked planet (the terminator ring has a double-horned profile), a day-to-night wind (a net shift), an
+ * east/west limb asymmetry; an instrument's measured line-spread function has the same form.  This stage convolves R,
+ * as it lies in device memory after a run, with a tabulated velocity kernel on the model's own non-uniform grid into a
+ * second buffer R_b, which then takes R's place as the input of the observe, velocity-map and expose calls with all
+ * their options.  A velocity-space kernel commutes with every Doppler factor those stages apply, so one pass per model
+ * evaluation serves all trials, taps, filters and orders.  All float64; every product, sum and difference is rounded
+ * on its own (no fused multiply-add), and the roundings named here are part of the definition.
+ *
+ *   inputs               wav[n_wav] finite, ascending (duplicates allowed) and > 0 (1 / wav[0] must be finite);
+ *                        R[n_orb][n_wav]; a kernel K[n_k], 2 <= n_k <= 1025, every entry finite and >= 0, not all
+ *                        zero, whose nodes sit at the Doppler offsets beta_i = b0 + i / s, b0 finite, s finite and > 0
+ *                        (nodes per unit beta).  K is piecewise linear between its nodes and zero outside them.
+ *                        The host forms D[i] = fl(K[i + 1] - K[i]) once
+ *   weights              q: the observation's trapezoid weights of the whole grid (both edges NaN,
+ *                        q_w = fl(fl(hi - lo) / 2) with hi, lo the neighbours or the end point itself).  There are no
+ *                        shard partials
+ *   per output w         r = fl(1 / wav[w])
+ *   per candidate w'     d = fl(wav[w'] - wav[w]), u = fl(d r), t = fl(fl(u - b0) s)
+ *   support              w' belongs when 0 <= t <= n_k - 1 (float64, both ends inclusive).  t is non-decreasing in w',
+ *                        so the support is one contiguous range
+ *   kernel value         i = min(floor(t), n_k - 2), a = t - i (exact), kern = fl(K[i] + fl(a D[i])) (>= 0 by the
+ *                        monotonicity of rounding), g = fl(kern q[w'])
+ *   sums                 num[o] and den start at +0 and take their terms in ascending w':
+ *                        num[o] = fl(num[o] + fl(g R[o][w'])), den = fl(den + g)
+ *   result               R_b[o][w] = num[o] / den (IEEE); NaN when den == 0, which covers an empty support (a pure
+ *                        shift kernel near an end of the grid)
+ *   NaN                  a NaN in R[o] reaches exactly the outputs of row o whose support holds it, members of weight
+ *                        zero included (0 NaN is NaN)
+ *   ends of the grid     the support is simply cut there and den normalises it
+ *   independence         R_b[o][w] depends on wav, R[o] and the kernel only: not on n_orb, the row's position, how rows
+ *                        are grouped, tile boundaries or whether values came from LDS or global memory.  Two calls
+ *                        agree bit for bit; there are no atomics
+ *   meaning              R_b(lambda) ~ int K(beta) R(lambda (1 + beta)) d beta / int K.  Absorbers at line-of-sight
+ *                        velocity v (positive: away from the observer) move a line to lambda (1 + v / c), so a velocity
+ *                        distribution P(v) is the kernel K(beta) = P(-beta c), to first order in v / c: the shift's
+ *                        error is (v / c)^2, about 1e-9 at 10 km/s */
+
+/* Make the kernel resident (the host array is read during the call only); n_k = 0 drops it.  PROM_E_ARG when a rule
+ * above is broken.  A new kernel, or none, ends the currency of a broadened spectrum (below). */
+int32_t prom_broaden_set(prom_ctx* ctx, int32_t n_k, double b0, double s, const double* K);
+/* The stage on a caller's spectrum: Rb_out[n_orb][n_wav].  PROM_E_STATE without a resident kernel; PROM_E_ARG for the
+ * checks of prom_spectrum_observe's spectrum and for a wavelength that is not > 0. */
+int32_t prom_spectrum_broaden(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                              double* Rb_out);
+/* Form R_b from the last run's R on its stream; nothing crosses the bus and the call does not wait.  From then until
+ * the next prom_transit_run, prom_transit_set, prom_transit_kernel_ms or prom_broaden_set, R_b is current:
+ * prom_transit_observe, prom_transit_vmap and every prom_transit_expose* read R_b in R's place (nothing else about
+ * them changes), while prom_transit_result and prom_transit_band_stats keep reading R.  prom_transit_observe with an
+ * edge that is not NaN then returns PROM_E_ARG: the stage needs the whole grid.  The run's wavelengths must obey the
+ * rules above (as for prom_transit_observe they are not checked again).  PROM_E_STATE without a resident kernel or a
+ * completed run. */
+int32_t prom_transit_broaden(prom_ctx* ctx);
+/* Copy the current R_b out: Rb_out[n_orb][n_wav].  PROM_E_STATE when none is current. */
+int32_t prom_transit_broadened(prom_ctx* ctx, double* Rb_out);
+/* Measurement aid (tools/broaden_bench.py), not for callers: ms_out[0] is the mean device duration in milliseconds of
+ * k_broaden over n_runs repetitions of the last broaden call's launch.  PROM_E_STATE when there is no such call. */
+int32_t prom_broaden_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
+
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop
  * events on its own dispatch packet (groups of kernels: the first start to the last stop).  ms_out[k] is

@@ -151,6 +151,11 @@ SIGNATURES = {
     "prom_spectrum_expose_orders": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, C.c_int32, _dp,
                                                 C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), _dp, _dp]),
     "prom_orders_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
+    "prom_broaden_set": (C.c_int32, [C.c_void_p, C.c_int32, C.c_double, C.c_double, _dp]),
+    "prom_spectrum_broaden": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, _dp]),
+    "prom_transit_broaden": (C.c_int32, [C.c_void_p]),
+    "prom_transit_broadened": (C.c_int32, [C.c_void_p, _dp]),
+    "prom_broaden_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -278,6 +283,7 @@ class Device:
         self._hp_key = None
         self._od_key = None
         self._od_n_seg = 0
+        self._br_key = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -812,6 +818,55 @@ class Device:
         ms = (C.c_double * 2)()
         self._check(self.lib.prom_orders_kernel_ms(self.h, int(n_runs), ms), "prom_orders_kernel_ms")
         return float(ms[0]), float(ms[1])
+
+    # ---- broadened spectra (prom_hip.h "broadened spectra on the device") -----------------------
+    def broaden_set(self, K, b0: float, s: float, key=None) -> None:
+        """prom_broaden_set: the velocity kernel K [n_k] (2 <= n_k <= 1025, >= 0) with nodes at the Doppler offsets
+        b0 + i / s.  ``key``: any value the caller keeps in ``broaden_key`` to skip a later upload of the same
+        kernel."""
+        K = _f64(K)
+        if K.ndim != 1:
+            raise ValueError("broaden_set: K must be a 1-D array")
+        self._br_key = None
+        self._check(self.lib.prom_broaden_set(self.h, len(K), float(b0), float(s), _d(K)), "prom_broaden_set")
+        self._br_key = key
+
+    def broaden_drop(self) -> None:
+        """prom_broaden_set with n_k = 0: no kernel is resident any more."""
+        self._br_key = None
+        self._check(self.lib.prom_broaden_set(self.h, 0, 0.0, 1.0, None), "prom_broaden_set")
+
+    @property
+    def broaden_key(self):
+        """The ``key`` of the kernel resident on the context (None: none, or set without a key)."""
+        return self._br_key
+
+    def spectrum_broaden(self, wav, R) -> np.ndarray:
+        """prom_spectrum_broaden of R[n_orb][n_wav] on the ascending, positive grid wav: R_b[n_orb][n_wav]."""
+        wav, R = _f64(wav), _f64(R)
+        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
+            raise ValueError("spectrum_broaden: R must be [n_orb][n_wav]")
+        out = np.empty(R.shape)
+        self._check(self.lib.prom_spectrum_broaden(self.h, R.shape[0], len(wav), _d(wav), _d(R), _d(out)),
+                    "prom_spectrum_broaden")
+        return out
+
+    def transit_broaden(self) -> None:
+        """prom_transit_broaden: R_b of the last run's R; the transit observe, vmap and expose calls read it until
+        the next run."""
+        self._check(self.lib.prom_transit_broaden(self.h), "prom_transit_broaden")
+
+    def transit_broadened(self) -> np.ndarray:
+        """prom_transit_broadened: the current R_b, [n_orb, n_wav]."""
+        out = np.empty(getattr(self, "_shape", (1, 1)))   # (no problem set yet: the library refuses)
+        self._check(self.lib.prom_transit_broadened(self.h, _d(out)), "prom_transit_broadened")
+        return out
+
+    def broaden_kernel_ms(self, n_runs: int = 20) -> float:
+        """prom_broaden_kernel_ms: mean device duration [ms] of k_broaden for the last broaden call's launch."""
+        ms = C.c_double(0.0)
+        self._check(self.lib.prom_broaden_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_broaden_kernel_ms")
+        return float(ms.value)
 
     # ---- stellar disk -----------------------------------------------------------------------
     def star_disk_flux(self, table_id: int, shift, clv, rho, dphi: float, drho: float, wavelength) -> np.ndarray:

@@ -16,6 +16,7 @@
 #include "detrend_index.h"
 #include "highpass_index.h"
 #include "order_index.h"
+#include "broaden_index.h"
 
 using prom::DevBuf;
 using prom::Error;
@@ -586,6 +587,7 @@ int32_t prom_transit_set(prom_ctx* ctx, const prom_transit_problem* pb) {
     prom::TransitDev& tr = ctx->tr;
     tr.ready = false;
     tr.ran = false;
+    ctx->br.current = false;   // R_b belongs to the run it was formed from
     // sigma-segment cache key of this set (committed at the end, after the device copy succeeded)
     bool seg_key_new = false, seg_key_keep = false;
     std::vector<double> new_key_sh;
@@ -607,6 +609,8 @@ int32_t prom_transit_set(prom_ctx* ctx, const prom_transit_problem* pb) {
     ctx->vm.last_wav = ctx->vm.last_R = nullptr;
     if (ctx->ex.set && ctx->ex.n_orb != pb->n_orb) ctx->ex.set = false;      // ... and the exposure table's rows
     ctx->ex.last_wav = ctx->ex.last_R = nullptr;
+    ctx->br.last_wav = ctx->br.last_q = ctx->br.last_R = nullptr;   // ... and those prom_transit_broaden read
+    ctx->br.last_out = nullptr;
     tr.n_x = pb->n_x;
     tr.n_sc = pb->n_scenarios;
     tr.n_moons = pb->n_moons;
@@ -1501,6 +1505,7 @@ int32_t prom_transit_run(prom_ctx* ctx, prom_transit_stats* stats) {
     tr.ts_blocks = 0;
 
     tr.ran = true;
+    ctx->br.current = false;   // the transit observe calls read this run's R until prom_transit_broaden is called again
     if (stats) {
       std::memset(stats, 0, sizeof(*stats));
       PROM_HIP(hipEventSynchronize(ev[3]));
@@ -1622,6 +1627,7 @@ int32_t prom_transit_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
     for (auto e : ev) PROM_HIP(hipEventDestroy(e));
     tr.last = 0;
     tr.ran = true;
+    ctx->br.current = false;
     for (int k = 0; k < PROM_K_COUNT; ++k) ms_out[k] = cnt[k] ? sum[k] / cnt[k] : std::nan("");
   });
 }
@@ -1818,6 +1824,13 @@ int32_t prom_timing_end(prom_ctx* ctx, int32_t max_runs, double* ms, int32_t* n_
 // ------------------------------------------------------------------------------ observation
 static bool obs_finite(double v) { return std::isfinite(v); }
 
+// the spectrum the transit observe calls read: the last run's R, or its broadened R_b while that is current
+// (prom_transit_broaden)
+static const double* transit_R(prom_ctx* ctx) {
+  const prom::TransitDev& tr = ctx->tr;
+  return ctx->br.current ? ctx->br.Rb.as<double>() : tr.slot[tr.last].R.as<double>();
+}
+
 int32_t prom_observe_set(prom_ctx* ctx, int32_t n_pix, const double* lam, const double* sig, double k, int32_t n_orb,
                          const double* f, const double* data, const double* ivar) {
   return guarded(ctx, [&] {
@@ -1909,9 +1922,11 @@ int32_t prom_transit_observe(prom_ctx* ctx, double edge_lo, double edge_hi, doub
     observe_check(ob, "prom_transit_observe", edge_lo, edge_hi, chi2_out || n_used_out);
     if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_observe: no completed run");
     if (ob.n_orb != tr.n_orb) throw Error(PROM_E_STATE, "prom_transit_observe: the observation has another n_orb");
+    PROM_REQUIRE(!ctx->br.current || (edge_lo != edge_lo && edge_hi != edge_hi),
+                 "prom_transit_observe: the broadened spectrum covers the whole grid (both edges NaN)");
     if (ob.n_pix == 0) return;
     // the last run's stream orders the observation after it
-    observe_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, edge_lo,
+    observe_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, edge_lo,
                edge_hi, num_out, den_out, chi2_out, n_used_out);
   });
 }
@@ -2046,7 +2061,7 @@ int32_t prom_transit_vmap(prom_ctx* ctx, double* mom_out, int64_t* n_used_out) {
     if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_vmap: no completed run");
     if (ctx->vm.n_orb != tr.n_orb) throw Error(PROM_E_STATE, "prom_transit_vmap: the trial table has another n_orb");
     // the last run's stream orders the map after it
-    vmap_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, mom_out,
+    vmap_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, mom_out,
             n_used_out);
   });
 }
@@ -2201,7 +2216,7 @@ int32_t prom_transit_expose(prom_ctx* ctx, double* mom_out, int64_t* n_used_out,
     if (ctx->ex.n_orb != tr.n_orb)
       throw Error(PROM_E_STATE, "prom_transit_expose: the exposure table has another n_orb");
     // the last run's stream orders the exposures after it
-    expose_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, mom_out,
+    expose_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, mom_out,
               n_used_out, model_out);
   });
 }
@@ -2352,7 +2367,7 @@ int32_t prom_transit_expose_detrended(prom_ctx* ctx, double* mom_out, int64_t* n
     if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose_detrended: no completed run");
     if (ctx->ex.n_orb != tr.n_orb)
       throw Error(PROM_E_STATE, "prom_transit_expose_detrended: the exposure table has another n_orb");
-    detrend_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, mom_out,
+    detrend_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, mom_out,
                n_used_out, model_out);
   });
 }
@@ -2521,7 +2536,7 @@ int32_t prom_transit_expose_highpass(prom_ctx* ctx, int32_t detrend, double* mom
     if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose_highpass: no completed run");
     if (ctx->ex.n_orb != tr.n_orb)
       throw Error(PROM_E_STATE, "prom_transit_expose_highpass: the exposure table has another n_orb");
-    highpass_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, detrend,
+    highpass_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, detrend,
                 mom_out, n_used_out, model_out);
   });
 }
@@ -2725,7 +2740,7 @@ int32_t prom_transit_expose_orders(prom_ctx* ctx, int32_t highpass, int32_t detr
     if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose_orders: no completed run");
     if (ctx->ex.n_orb != tr.n_orb)
       throw Error(PROM_E_STATE, "prom_transit_expose_orders: the exposure table has another n_orb");
-    orders_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), tr.slot[tr.last].R.as<double>(), tr.n_wav, highpass,
+    orders_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, highpass,
               detrend, mom_out, n_used_out, orec_mom_out, orec_n_used_out, tot_out, model_out);
   });
 }
@@ -2777,6 +2792,147 @@ int32_t prom_orders_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
     }
     ms_out[0] = scale * sum[0] / n_runs;
     ms_out[1] = scale * sum[1] / n_runs;
+  });
+}
+
+// ------------------------------------------------------------------------------ broadened spectra
+int32_t prom_broaden_set(prom_ctx* ctx, int32_t n_k, double b0, double s, const double* K) {
+  return guarded(ctx, [&] {
+    prom::BrDev& br = ctx->br;
+    br.set = false;
+    br.current = false;   // R_b was formed with the kernel that leaves
+    br.last_wav = br.last_q = br.last_R = nullptr;
+    br.last_out = nullptr;
+    if (n_k == 0) return;
+    PROM_REQUIRE(n_k >= 2 && n_k <= prom::kBrMaxNodes && K, "prom_broaden_set: n_k must be 0 or lie in [2, 1025]");
+    PROM_REQUIRE(obs_finite(b0), "prom_broaden_set: b0 must be finite");
+    PROM_REQUIRE(obs_finite(s) && s > 0.0, "prom_broaden_set: s must be finite and > 0");
+    bool any = false;
+    for (int32_t i = 0; i < n_k; ++i) {
+      PROM_REQUIRE(obs_finite(K[i]) && K[i] >= 0.0, "prom_broaden_set: K must be finite and >= 0");
+      any = any || K[i] > 0.0;
+    }
+    PROM_REQUIRE(any, "prom_broaden_set: K must not be all zero");
+    std::vector<prom::BrRec> rec((size_t)n_k);
+    for (int32_t i = 0; i < n_k; ++i) rec[i] = prom::BrRec{K[i], i + 1 < n_k ? K[i + 1] - K[i] : 0.0};
+    const hipStream_t st = ctx->stream;
+    for (auto t : ctx->streams) PROM_HIP(hipStreamSynchronize(t));   // (a launch in flight may read the old records)
+    upload(br.rec, rec.data(), n_k, st);
+    PROM_HIP(hipStreamSynchronize(st));   // the host array is read during the call only
+    br.n_k = n_k;
+    br.b0 = b0;
+    br.s = s;
+    br.set = true;
+  });
+}
+
+// q of the whole grid and k_broaden on stream st (ev: events around k_broaden)
+static void broaden_launch(prom_ctx* ctx, hipStream_t st, const double* wav, double* q, const double* R, int32_t n_wav,
+                           int32_t n_orb, double* out) {
+  prom::BrDev& br = ctx->br;
+  const double nan = std::nan("");
+  prom::launch_observe_q(st, wav, n_wav, nan, nan, q);
+  prom::launch_broaden(st, wav, q, R, n_wav, n_orb, br.rec.as<prom::BrRec>(), prom::BrKern{br.b0, br.s, br.n_k}, out,
+                       nullptr, nullptr);
+  br.last_wav = wav;
+  br.last_q = q;
+  br.last_R = R;
+  br.last_out = out;
+  br.last_n_wav = n_wav;
+  br.last_n_orb = n_orb;
+}
+
+int32_t prom_spectrum_broaden(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                              double* Rb_out) {
+  return guarded(ctx, [&] {
+    prom::BrDev& br = ctx->br;
+    if (!br.set) throw Error(PROM_E_STATE, "prom_spectrum_broaden: no kernel on the context (prom_broaden_set)");
+    PROM_REQUIRE(n_orb >= 1 && n_orb <= 65535, "prom_spectrum_broaden: bad n_orb");
+    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R && Rb_out, "prom_spectrum_broaden: bad spectrum");
+    for (int64_t w = 0; w < n_wav; ++w)
+      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
+                   "prom_spectrum_broaden: wavelengths must be finite and ascending");
+    PROM_REQUIRE(wav[0] > 0.0 && obs_finite(1.0 / wav[0]),
+                 "prom_spectrum_broaden: wavelengths must be > 0 (and 1 / wav finite)");
+    const hipStream_t st = ctx->stream;
+    const int64_t n = (int64_t)n_orb * n_wav;
+    br.last_wav = br.last_q = br.last_R = nullptr;   // (the uploads may move the buffers the last call read)
+    br.last_out = nullptr;
+    upload(br.wav, wav, n_wav, st);
+    upload(br.R, R, n, st);
+    br.sq.ensure(sizeof(double) * (size_t)n_wav);
+    br.out.ensure(sizeof(double) * (size_t)n);
+    broaden_launch(ctx, st, br.wav.as<double>(), br.sq.as<double>(), br.R.as<double>(), (int32_t)n_wav, n_orb,
+                   br.out.as<double>());
+    download(Rb_out, br.out, n, st);
+    PROM_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int32_t prom_transit_broaden(prom_ctx* ctx) {
+  return guarded(ctx, [&] {
+    prom::TransitDev& tr = ctx->tr;
+    prom::BrDev& br = ctx->br;
+    if (!br.set) throw Error(PROM_E_STATE, "prom_transit_broaden: no kernel on the context (prom_broaden_set)");
+    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_broaden: no completed run");
+    const hipStream_t st = ctx->streams[tr.last];
+    // R_b and q are one buffer each: an earlier broaden on another stream must be through with them
+    if (br.stream && br.stream != st) PROM_HIP(hipStreamSynchronize(br.stream));
+    const size_t bytes = sizeof(double) * (size_t)tr.n_orb * (size_t)tr.n_wav;
+    if (bytes > br.Rb.cap || sizeof(double) * (size_t)tr.n_wav > br.q.cap) {
+      // the buffers move: nothing may read the old ones any more, and no measurement aid may repeat a call on them
+      for (auto t : ctx->streams) PROM_HIP(hipStreamSynchronize(t));
+      const double* old = br.Rb.as<double>();
+      if (old && ctx->obs.last_R == old) ctx->obs.last_wav = ctx->obs.last_R = nullptr;
+      if (old && ctx->vm.last_R == old) ctx->vm.last_wav = ctx->vm.last_R = nullptr;
+      if (old && ctx->ex.last_R == old) {
+        ctx->ex.last_wav = ctx->ex.last_R = nullptr;
+        ctx->ex.dt_ran = ctx->ex.hp_ran = ctx->ex.od_ran = false;
+      }
+      br.last_wav = br.last_q = br.last_R = nullptr;
+      br.last_out = nullptr;
+    }
+    br.current = false;
+    br.q.ensure(sizeof(double) * (size_t)tr.n_wav);
+    br.Rb.ensure(bytes);
+    broaden_launch(ctx, st, tr.wav.as<double>(), br.q.as<double>(), tr.slot[tr.last].R.as<double>(), (int32_t)tr.n_wav,
+                   tr.n_orb, br.Rb.as<double>());
+    br.stream = st;
+    br.current = true;
+  });
+}
+
+int32_t prom_transit_broadened(prom_ctx* ctx, double* Rb_out) {
+  return guarded(ctx, [&] {
+    prom::TransitDev& tr = ctx->tr;
+    prom::BrDev& br = ctx->br;
+    if (!tr.ran || !br.current)
+      throw Error(PROM_E_STATE, "prom_transit_broadened: no broadened spectrum of the last run (prom_transit_broaden)");
+    PROM_REQUIRE(Rb_out, "prom_transit_broadened: null output");
+    const hipStream_t st = br.stream;
+    download(Rb_out, br.Rb, (int64_t)tr.n_orb * tr.n_wav, st);
+    PROM_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int32_t prom_broaden_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
+  return guarded(ctx, [&] {
+    prom::BrDev& br = ctx->br;
+    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_broaden_kernel_ms: bad arguments");
+    if (!br.set || !br.last_wav) throw Error(PROM_E_STATE, "prom_broaden_kernel_ms: no broaden call to repeat");
+    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
+    const hipStream_t st = ctx->stream;
+    double sum = 0.0;
+    for (int32_t r = 0; r < n_runs; ++r) {
+      prom::launch_broaden(st, br.last_wav, br.last_q, br.last_R, br.last_n_wav, br.last_n_orb,
+                           br.rec.as<prom::BrRec>(), prom::BrKern{br.b0, br.s, br.n_k}, br.last_out, ctx->ev[0],
+                           ctx->ev[1]);
+      PROM_HIP(hipStreamSynchronize(st));
+      float ms = 0.0f;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      sum += ms;
+    }
+    *ms_out = sum / n_runs;
   });
 }
 

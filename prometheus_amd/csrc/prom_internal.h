@@ -478,6 +478,25 @@ struct ExDev {
   bool od_ran = false;                    // the last call was a per-order one: its final model and flags are resident
 };
 
+// The velocity kernel resident on a context (prom_broaden_set), the broadened spectrum R_b of the last run and the
+// work buffers of the broaden calls.
+struct BrDev {
+  bool set = false;
+  int32_t n_k = 0;
+  double b0 = 0.0, s = 0.0;
+  DevBuf rec;                             // [n_k] BrRec {K[i], D[i]}
+  DevBuf q, Rb;                           // prom_transit_broaden: [n_wav], R_b[n_orb][n_wav]
+  bool current = false;                   // Rb is the last run's R broadened: the transit observe calls read it
+  hipStream_t stream = nullptr;           // the stream the last prom_transit_broaden ran on
+  DevBuf wav, R, sq, out;                 // prom_spectrum_broaden's copies of the caller's spectrum, its q and its R_b
+  // the last k_broaden launch, for prom_broaden_kernel_ms to repeat (null: none yet)
+  const double* last_wav = nullptr;
+  const double* last_q = nullptr;
+  const double* last_R = nullptr;
+  double* last_out = nullptr;
+  int32_t last_n_wav = 0, last_n_orb = 0;
+};
+
 }  // namespace prom
 
 struct prom_ctx {
@@ -493,6 +512,7 @@ struct prom_ctx {
   prom::ObsDev obs;
   prom::VmDev vm;
   prom::ExDev ex;
+  prom::BrDev br;
   int64_t vmap_scratch_bytes = (int64_t)256 << 20;   // PROM_VMAP_SCRATCH_MB: cap of k_vmap's partial records
   prom::DevBuf scratch[6];
   bool timing = false;
@@ -623,6 +643,11 @@ void launch_order_moments(hipStream_t s, const double* model, const uint8_t* fla
                           hipEvent_t ev0, hipEvent_t ev1);
 void launch_order_totals(hipStream_t s, const double* orec, const uint8_t* keep, int32_t n_exp, int32_t n_trial,
                          int32_t j_first, int32_t nb, int32_t n_seg, double* tot, hipEvent_t ev0, hipEvent_t ev1);
+// broadened spectra (prom_broaden.hip): Rb[n_orb][n_wav] from R, the trapezoid weights q and the kernel's records
+struct BrRec;
+struct BrKern;
+void launch_broaden(hipStream_t s, const double* wav, const double* q, const double* R, int32_t n_wav, int32_t n_orb,
+                    const BrRec* rec, const BrKern& kern, double* Rb, hipEvent_t ev0, hipEvent_t ev1);
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

@@ -576,12 +576,34 @@ class WavelengthGrid:
 
 
 # ============================================================================== transit
+def _upload_broadening(dev, br) -> None:
+    """The velocity kernel of a job goes to the device once while its content key is unchanged."""
+    if br is not None and dev.broaden_key != br.key:
+        dev.broaden_set(br.K, br.b0, br.s, key=br.key)
+
+
+def _check_broadening(broaden, who, n_devices, n_wav, chunk) -> None:
+    """``broaden`` of Transit.observe / velocity_map / expose / broadened: TypeError for anything but a Broadening,
+    ValueError for a run that would be split, both before a device is touched."""
+    from . import observation as obs
+    if broaden is None:
+        return
+    if not isinstance(broaden, obs.Broadening):
+        raise TypeError("%s: broaden must be an observation.Broadening" % who)
+    if n_devices != 1 or n_wav > chunk:
+        raise ValueError(
+            "%s: the run would be split into %d wavelength shard(s) and chunks of %d wavelengths (the grid has %d); "
+            "the broadening convolves R over the whole grid (an output near a cut needs the neighbour's R).  Give one "
+            "device and raise max_memory_gb until the grid fits one chunk." % (who, n_devices, chunk, n_wav))
+
+
 class _ObserveJob:
     """One Transit.observe call inside _integrate: the observation's upload per device, the observe call after
     each chunk's run and the sum of the partials."""
 
-    def __init__(self, observation, want_model):
+    def __init__(self, observation, want_model, broaden=None):
         o = observation
+        self.br = broaden
         self.ins, self.n_orb, self.f, self.data, self.ivar, self.key = o.instrument, o.n_orb, o.f, o.data, o.ivar, o.key
         self.want_model = want_model
         self.whole = False        # one device, one chunk: the call sees the whole grid
@@ -594,11 +616,16 @@ class _ObserveJob:
         if dev.observe_key != self.key:   # a retrieval loop uploads its observation once
             dev.observe_set(self.ins.lam, self.ins.sig, self.ins.truncate, self.n_orb, self.f, self.data, self.ivar,
                             key=self.key)
+        _upload_broadening(dev, self.br)
 
     def run(self, dev, wavelength, a: int, b: int):
         lo = wavelength[a - 1] if a > 0 else np.nan
         hi = wavelength[b] if b < len(wavelength) else np.nan
         dev_chi2 = self.whole and self.data is not None
+        if self.br is not None:
+            if not self.whole:   # (observe refuses such a run before it starts)
+                raise RuntimeError("observe: the run was split into wavelength shards or chunks")
+            dev.transit_broaden()
         return dev.transit_observe(lo, hi, partials=self.want_model or not dev_chi2, chi2=dev_chi2)
 
     def add(self, part) -> None:
@@ -627,8 +654,9 @@ class _VmapJob:
     """One Transit.velocity_map call inside _integrate: the observation and the trial table go to the device once
     each while their content keys are unchanged, then the map runs over the (one) chunk's R."""
 
-    def __init__(self, observation, factors):
-        self.obs = _ObserveJob(observation, False)
+    def __init__(self, observation, factors, broaden=None):
+        self.obs = _ObserveJob(observation, False, broaden)
+        self.br = broaden
         self.F = factors
         self.key = (observation.key,) + _content_fingerprint(factors)
         self.whole = False
@@ -642,6 +670,8 @@ class _VmapJob:
     def run(self, dev, wavelength, a: int, b: int):
         if not self.whole:   # (velocity_map refuses such a run before it starts)
             raise RuntimeError("velocity_map: the run was split into wavelength shards or chunks")
+        if self.br is not None:
+            dev.transit_broaden()
         return dev.transit_vmap()
 
     def add(self, part) -> None:
@@ -652,9 +682,11 @@ class _ExposeJob:
     """One Transit.expose call inside _integrate: the pixels and the exposure table go to the device once each while
     their content keys are unchanged, then the exposures run over the (one) chunk's R."""
 
-    def __init__(self, exposures, n_orb, want_model, detrend=None, highpass=None, orders=None, order_records=True):
+    def __init__(self, exposures, n_orb, want_model, detrend=None, highpass=None, orders=None, order_records=True,
+                 broaden=None):
         self.ex = exposures
-        self.obs = _ObserveJob(exposures.pixels(n_orb), False)
+        self.obs = _ObserveJob(exposures.pixels(n_orb), False, broaden)
+        self.br = broaden
         self.want_model = want_model
         self.dt = detrend
         self.hp = highpass
@@ -678,6 +710,8 @@ class _ExposeJob:
     def run(self, dev, wavelength, a: int, b: int):
         if not self.whole:   # (expose refuses such a run before it starts)
             raise RuntimeError("expose: the run was split into wavelength shards or chunks")
+        if self.br is not None:
+            dev.transit_broaden()
         if self.od is not None:
             mom, nu, self.order_moments, self.order_n_used, self.order_totals, model = dev.transit_expose_orders(
                 highpass=self.hp is not None, detrend=self.dt is not None, moments=True, records=self.od_records,
@@ -691,6 +725,28 @@ class _ExposeJob:
 
     def add(self, part) -> None:
         self.moments, self.n_used, self.model = part
+
+
+class _BroadenedJob:
+    """One Transit.broadened call inside _integrate: the kernel goes to the device once while its content key is
+    unchanged, then R_b of the (one) chunk's R comes back."""
+
+    def __init__(self, broaden):
+        self.br = broaden
+        self.whole = False
+        self.Rb = None
+
+    def upload(self, dev) -> None:
+        _upload_broadening(dev, self.br)
+
+    def run(self, dev, wavelength, a: int, b: int):
+        if not self.whole:   # (broadened refuses such a run before it starts)
+            raise RuntimeError("broadened: the run was split into wavelength shards or chunks")
+        dev.transit_broaden()
+        return dev.transit_broadened()
+
+    def add(self, part) -> None:
+        self.Rb = part
 
 
 _STAR_TABLES: "weakref.WeakKeyDictionary" = None
@@ -887,7 +943,7 @@ class Transit:
 
     def observe(self, instrument, frame_shifts=None, data=None, err=None, devices: Optional[Sequence[int]] = None,
                 max_memory_gb: float = 2.0, return_model: bool = True, return_spectrum: bool = False,
-                cull_tau: float = 0.0, options: int = 0):
+                cull_tau: float = 0.0, options: int = 0, *, broaden=None):
         """Run the transit and observe R on the device: R convolved with the instrument's Gaussian line-spread
         function and sampled on its pixels, per phase in the frame scaled by ``frame_shifts`` [n_orb] (None: the
         model's own frame; observation.planet_frame_shifts: the planet's rest frame), and with ``data``
@@ -901,9 +957,22 @@ class Transit:
 
         ``instrument`` may be an observation.Observation (instrument, frame, data and err prepared once): a device
         that already holds it is not sent it again, and nothing is hashed per call.  With an Instrument, every call
-        sorts and hashes data and err anew (82 MB for 16 phases of 320,000 pixels: milliseconds of host time)."""
+        sorts and hashes data and err anew (82 MB for 16 phases of 320,000 pixels: milliseconds of host time).
+
+        ``broaden``: an observation.Broadening.  R is then convolved with that velocity kernel on the device, on the
+        model's own grid, before the instrument sees it (include/prom_hip.h, "broadened spectra on the device");
+        ``spectrum`` stays the unbroadened R.  The kernel is uploaded once while its content is unchanged.  The stage
+        needs the whole grid, so the run must be one wavelength shard on one device (default 0) in one chunk:
+        otherwise ValueError; TypeError for anything but a Broadening; both before a device is touched.  With None
+        nothing changes."""
         from . import observation as obs
         n_orb = len(self.spatialGrid.constructOrbphaseAxis())
+        if broaden is not None:
+            if not hasattr(self, "wavelength"):
+                self.addWavelength()
+            devices = [0] if devices is None else list(devices)
+            _check_broadening(broaden, "observe", len(devices), len(self.wavelength),
+                              self._wavelength_chunk(max_memory_gb, n_orb))
         if isinstance(instrument, obs.Observation):
             if frame_shifts is not None or data is not None or err is not None:
                 raise ValueError("observe: an Observation already holds frame_shifts, data and err")
@@ -912,12 +981,13 @@ class Transit:
             observation = instrument
         else:
             observation = obs.Observation(instrument, n_orb, frame_shifts, data, err)
-        job = _ObserveJob(observation, return_model)
+        job = _ObserveJob(observation, return_model, broaden)
         R, _ = self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=return_spectrum, observe=job)
         return job.result(obs, R)
 
     def velocity_map(self, observation, factors, devices: Optional[Sequence[int]] = None,
-                     max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0):
+                     max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0, *,
+                     broaden=None):
         """Run the transit and map it against data over a table of trial frames on the device: ``observation`` is an
         observation.Observation with data and err (its own frame_shifts are not applied), ``factors`` the table
         F[n_orb][n_trial] of frame factors (observation.trial_factors, observation.kp_vsys_factors).  R stays in
@@ -929,8 +999,14 @@ class Transit:
         The moments are not additive over wavelength partials (M = num / den needs every shard's sums before it meets
         the data), so the run must be one wavelength shard on one device in one chunk: otherwise ValueError, before
         anything is uploaded or run.  ``devices``: one GPU id (default 0); ``max_memory_gb`` (default 2) bounds the
-        chunk as in sumOverChords."""
+        chunk as in sumOverChords.
+
+        ``broaden``: an observation.Broadening; the map then reads R convolved with that velocity kernel on the device
+        (Transit.observe has the details).  TypeError for anything else, before a device is touched.  With None nothing
+        changes."""
         from . import observation as obs
+        if broaden is not None and not isinstance(broaden, obs.Broadening):
+            raise TypeError("velocity_map: broaden must be an observation.Broadening")
         if not isinstance(observation, obs.Observation):
             raise TypeError("velocity_map: observation must be an observation.Observation")
         if observation.data is None:
@@ -956,13 +1032,13 @@ class Transit:
                 "the sums of the whole grid before it meets the data).  Give one device and raise max_memory_gb "
                 "until the grid fits one chunk, or observe per trial with Transit.observe, which combines partials."
                 % (len(devices), chunk, n_wav))
-        job = _VmapJob(observation, F)
+        job = _VmapJob(observation, F, broaden)
         self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
         return obs.VelocityMap(job.moments, job.n_used, F)
 
     def expose(self, exposures, return_model: bool = False, devices: Optional[Sequence[int]] = None,
                max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0, *, detrend=None,
-               highpass=None, orders=None, order_records: bool = True):
+               highpass=None, orders=None, order_records: bool = True, broaden=None):
         """Run the transit and compare it on the device with exposures taken at any phase and smeared over their
         duration: ``exposures`` is an observation.Exposures (rows, weights and factors from
         observation.exposure_taps, data and err per exposure).  R stays in device memory; per (exposure, trial) the
@@ -995,10 +1071,16 @@ class Transit:
         (observation.OrderTotals: loglike, chi2, chi2_scaled and n_used over the kept orders with two used pixels at
         least, each [n_exp][n_trial], formed on the device: 32 bytes per (exposure, trial) cross the bus).  The orders
         are uploaded once while their content is unchanged, and the model of all trials lies in device memory at once.
-        TypeError and ValueError as for ``detrend``.  With None nothing changes."""
+        TypeError and ValueError as for ``detrend``.  With None nothing changes.
+
+        ``broaden``: an observation.Broadening; the exposures, with every filter and the orders, then read R convolved
+        with that velocity kernel on the device (Transit.observe has the details): one pass over R serves every trial
+        and tap.  TypeError for anything else, before a device is touched.  With None nothing changes."""
         from . import observation as obs
         if not isinstance(exposures, obs.Exposures):
             raise TypeError("expose: exposures must be an observation.Exposures")
+        if broaden is not None and not isinstance(broaden, obs.Broadening):
+            raise TypeError("expose: broaden must be an observation.Broadening")
         if detrend is not None:
             if not isinstance(detrend, obs.Detrend):
                 raise TypeError("expose: detrend must be an observation.Detrend")
@@ -1029,7 +1111,7 @@ class Transit:
                 "has %d); the moments are not additive over wavelength partials (a tap's model M = num / den needs "
                 "the sums of the whole grid before it meets the data).  Give one device and raise max_memory_gb "
                 "until the grid fits one chunk." % (len(devices), chunk, n_wav))
-        job = _ExposeJob(exposures, n_orb, return_model, detrend, highpass, orders, order_records)
+        job = _ExposeJob(exposures, n_orb, return_model, detrend, highpass, orders, order_records, broaden)
         self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
         model = exposures.instrument.unsort(job.model) if return_model else None
         vm = obs.VelocityMap(job.moments, job.n_used, exposures.factors, model=model)
@@ -1039,6 +1121,24 @@ class Transit:
                 vm.by_order = obs.OrderMap(job.order_moments, job.order_n_used, orders.labels, orders.keep)
             vm.order_totals = obs.OrderTotals(job.order_totals)
         return vm
+
+    def broadened(self, broadening, devices: Optional[Sequence[int]] = None, max_memory_gb: Optional[float] = None,
+                  cull_tau: float = 0.0, options: int = 0) -> np.ndarray:
+        """Run the transit and return R_b[n_orb, n_wav]: R convolved on the device with the velocity kernel
+        ``broadening`` (an observation.Broadening), as Transit.observe / velocity_map / expose(broaden=...) see it; for
+        inspection.  One device and one chunk as there: otherwise ValueError; TypeError for anything but a Broadening."""
+        n_orb = len(self.spatialGrid.constructOrbphaseAxis())
+        if not hasattr(self, "wavelength"):
+            self.addWavelength()
+        devices = [0] if devices is None else list(devices)
+        max_memory_gb = 2.0 if max_memory_gb is None else max_memory_gb
+        if broadening is None:
+            raise TypeError("broadened: broadening must be an observation.Broadening")
+        _check_broadening(broadening, "broadened", len(devices), len(self.wavelength),
+                          self._wavelength_chunk(max_memory_gb, n_orb))
+        job = _BroadenedJob(broadening)
+        self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
+        return job.Rb
 
     def _wavelength_chunk(self, max_memory_gb, n_orb: int) -> int:
         """Wavelengths per device step under ``max_memory_gb``."""

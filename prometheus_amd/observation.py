@@ -434,6 +434,91 @@ class Orders:
                                                                     self.keep.astype(np.uint8))
 
 
+MAX_BROADENING_NODES = 1025   # of a velocity kernel (the device's record stage)
+
+
+class Broadening:
+    """The velocity kernel of Transit.observe / velocity_map / expose(broaden=...) and Transit.broadened: ``weights``
+    [n] (finite and >= 0, not all zero) are the shares of the absorbing gas at the line-of-sight velocities
+    ``velocities`` [n] in cm/s (positive: away from the observer), uniform and ascending, 2 <= n <= 1025; between the
+    nodes the distribution is linear, outside them zero.  R is convolved with it on the device, on the model's own
+    grid, before the instrument sees it (include/prom_hip.h, "broadened spectra on the device").  Gas at velocity v
+    moves a line to lambda (1 + v / c), so the device's kernel over the Doppler offset beta is K(beta) = P(-beta c):
+    the weights reversed, first node b0 = -velocities[-1] / c, s = c / step nodes per unit beta.  These and the content
+    key that lets a device skip the upload are computed once here; the arrays are copied.  TypeError or ValueError for
+    a bad shape or value, before a device is touched."""
+
+    def __init__(self, velocities, weights):
+        from . import constants as const
+        from .gasProperties import _content_fingerprint
+        try:
+            v = np.array(velocities, dtype=np.float64)
+            p = np.array(weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise TypeError("Broadening: velocities and weights must be arrays of numbers") from None
+        if v.ndim != 1 or p.shape != v.shape:
+            raise ValueError("Broadening: velocities and weights must be 1-D arrays of one length")
+        if not 2 <= len(v) <= MAX_BROADENING_NODES:
+            raise ValueError("Broadening: between 2 and %d nodes, not %d" % (MAX_BROADENING_NODES, len(v)))
+        if not (np.all(np.isfinite(v)) and np.all(np.isfinite(p))):
+            raise ValueError("Broadening: velocities and weights must be finite")
+        if np.any(p < 0) or not np.any(p > 0):
+            raise ValueError("Broadening: weights must be >= 0 and not all zero")
+        step = (v[-1] - v[0]) / (len(v) - 1)
+        if not (step > 0 and np.all(np.diff(v) > 0)):
+            raise ValueError("Broadening: velocities must be ascending")
+        if np.max(np.abs(v - (v[0] + step * np.arange(len(v))))) > 1e-9 * step * len(v):
+            raise ValueError("Broadening: velocities must be uniformly spaced")
+        self.velocities, self.weights = v, p
+        self.K = np.ascontiguousarray(p[::-1])       # what the device sees
+        self.b0 = float(-v[-1] / const.c)
+        self.s = float(const.c / step)
+        if not (math.isfinite(self.s) and self.s > 0):
+            raise ValueError("Broadening: the velocity step is too small")
+        self.key = ("broaden", self.b0, self.s) + _content_fingerprint(self.K)
+
+
+def rotation_kernel(v_eq: float, n: int = 65, wind: float = 0.0, east_west=(1.0, 1.0)):
+    """(velocities, weights) of the terminator ring of a rigid rotator with equatorial speed ``v_eq`` [cm/s]: gas on
+    the ring has P(v) ~ 1 / sqrt(v_eq^2 - v^2), the double-horned profile.  ``n`` uniform nodes span [-v_eq, v_eq]; a
+    node's weight is the exact integral of P over its cell (a difference of arcsines), so the horns stay integrable.
+    ``wind`` [cm/s] shifts all velocities (a day-to-night flow is negative: towards the observer).  ``east_west``
+    weighs the receding (v > 0) and the approaching (v < 0) half of the ring.  The weights sum to 1."""
+    v_eq, wind, n = float(v_eq), float(wind), int(n)
+    if not (math.isfinite(v_eq) and v_eq > 0 and math.isfinite(wind)):
+        raise ValueError("rotation_kernel: v_eq must be positive and wind finite")
+    if not 2 <= n <= MAX_BROADENING_NODES:
+        raise ValueError("rotation_kernel: between 2 and %d nodes" % MAX_BROADENING_NODES)
+    ew = np.array(east_west, dtype=np.float64)
+    if ew.shape != (2,) or not (np.all(np.isfinite(ew)) and np.all(ew >= 0) and np.any(ew > 0)):
+        raise ValueError("rotation_kernel: east_west must be two weights >= 0, not both zero")
+    x = np.linspace(-1.0, 1.0, n)                                  # nodes in units of v_eq
+    h = 1.0 / (n - 1)
+    lo, hi = np.clip(x - h, -1.0, 1.0), np.clip(x + h, -1.0, 1.0)  # the cells' ends
+    share = lambda a, b: (np.arcsin(b) - np.arcsin(a)) / math.pi   # of the ring between a <= b
+    w = ew[0] * share(np.maximum(lo, 0.0), np.maximum(hi, 0.0)) + ew[1] * share(np.minimum(lo, 0.0), np.minimum(hi, 0.0))
+    return x * v_eq + wind, w / w.sum()
+
+
+def gaussian_velocity_kernel(sigma_v: float, truncate: float = 4.0, n: int = 65):
+    """(velocities, weights) of a Gaussian velocity distribution of standard deviation ``sigma_v`` [cm/s] on ``n``
+    uniform nodes over [-truncate sigma_v, truncate sigma_v]; the weights sum to 1."""
+    sigma_v, truncate, n = float(sigma_v), float(truncate), int(n)
+    if not (math.isfinite(sigma_v) and sigma_v > 0 and math.isfinite(truncate) and truncate > 0):
+        raise ValueError("gaussian_velocity_kernel: sigma_v and truncate must be positive")
+    if not 2 <= n <= MAX_BROADENING_NODES:
+        raise ValueError("gaussian_velocity_kernel: between 2 and %d nodes" % MAX_BROADENING_NODES)
+    z = np.linspace(-truncate, truncate, n)
+    w = np.exp(-0.5 * z * z)
+    return z * sigma_v, w / w.sum()
+
+
+def tidally_locked_speed(planet) -> float:
+    """Equatorial rotation speed [cm/s] of a planet that rotates once per orbit: R_p sqrt(G M_star / a^3)."""
+    from . import constants as const
+    return float(planet.R * math.sqrt(const.G * planet.hostStar.M / planet.a ** 3))
+
+
 def model_spectrum(num, den) -> np.ndarray:
     """M = num / den; NaN where den == 0 (no model coverage)."""
     num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
