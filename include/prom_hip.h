@@ -671,6 +671,79 @@ int32_t prom_transit_broadened(prom_ctx* ctx, double* Rb_out);
  * k_broaden over n_runs repetitions of the last broaden call's launch.  PROM_E_STATE when there is no such call. */
 int32_t prom_broaden_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
 
+/* ---- injection and SYSREM on the device ---------------------------------------------------------
+ * To quote a detection significance or to measure how much signal the cleaning eats, a model is multiplied into the
+ * RAW exposures at a chosen trial and strength, and the result is cleaned exactly as the real data were: the
+ * high-pass along each order, then SYSREM.  That is one SYSREM per injection, so it runs here on the device: U and the
+ * cleaned data come back, and the caller builds the exposure table and the filter of the recovery from them.  All
+ * float64.  Every product, sum, quotient and square root is rounded on its own, there is no fused multiply-add, and
+ * the order of every sum named here is part of the definition.
+ *
+ *   inputs               the resident observation and exposure table (prom_expose_set: n_exp, n_pix, ivar), resident
+ *                        raw data raw[n_exp][n_pix] in the device's pixel order, any value allowed (NaN marks a bad
+ *                        pixel), n_exp <= 4096; optionally the resident high-pass (prom_highpass_set); for an
+ *                        injection a spectrum over the whole grid, a trial j and a finite scale
+ *   injection            M[e][p] is prom_spectrum_expose's model_out[e][j][p], bit for bit (unfiltered; formed from
+ *                        the broadened R while that is current).  D[e][p] = fl(raw fl(1 + fl(scale fl(M - 1)))) where
+ *                        M is not NaN, and raw where M is NaN: a pixel outside the model carries no planet.  Without
+ *                        an injection D = raw
+ *   high-pass            on request (highpass = 1) D goes through the resident high-pass as the model of one trial
+ *                        would, row by row, exactly as defined under "high-pass filtered exposures on the device"
+ *   weights              w[e][p] = ivar[e][p] when ivar is finite and > 0 and D (after the high-pass) is finite, else
+ *                        0.  r = D where w > 0, else +0
+ *   column fit fit_c(a)  per pixel p, num and den start at +0; in ascending e, a term with w = 0 is skipped, the others
+ *                        give num = fl(num + fl(fl(w r) a_e)) and den = fl(den + fl(w fl(a_e a_e))).
+ *                        c_p = fl(num / den) when den > 0, else +0
+ *   row fit fit_a(c)     per exposure e the terms fl(fl(w r) c_p) of num_e and fl(w fl(c_p c_p)) of den_e over the
+ *                        pixels; a term with w = 0 adds nothing.  Both sums are added in one fixed shape, a function
+ *                        of n_pix alone (not of n_exp, n_comp, any environment knob or the launch), with V = 2:
+ *                          lane    the pixels are cut into groups of V consecutive pixels; a group's sum starts at +0
+ *                                  and takes its terms in ascending p
+ *                          tile    64 consecutive groups (a tile of T = 64 V = 128 pixels; the tail of the last tile
+ *                                  is groups of +0) are t[0 .. 63]; for m = 1, 2, 4, 8, 16, 32 in turn every t[l]
+ *                                  becomes fl(t[l] + t[l ^ m]) (all l at once), and t[0] is the tile's partial
+ *                          row     64 sums s[0 .. 63] start at +0; s[l] adds the partials of the tiles l, l + 64,
+ *                                  l + 128, ... in ascending order; the same butterfly over s gives the sum
+ *                        a_e = fl(num_e / den_e) when den_e > 0, else +0.  Then norm = sqrt of the sum, from +0 in
+ *                        ascending e, of fl(a_e a_e).  If norm > 0 is false the component ends: its column of U is +0
+ *                        and r stays as it is.  Otherwise a_e = fl(a_e / norm)
+ *   component            starts with a_e = fl(1 / sqrt(n_exp)) for every e and c = fit_c(a); n_iter times a = fit_a(c)
+ *                        with its normalisation, then c = fit_c(a); then r[e][p] = fl(r - fl(a_e c_p)) where w > 0.
+ *                        a is the component's column of U.  With ones, first a = 1, c = fit_c(a), the same
+ *                        subtraction, and a leading column of ones in U.  0 <= n_comp, 1 <= n_comp + ones <= 16,
+ *                        n_iter >= 1
+ *   outputs              U[n_exp][n_comp + ones]; cleaned[e][p] = r where w > 0, else the value of D as it came; on
+ *                        request injected[e][p] = D after the injection and the high-pass, before SYSREM
+ *   independence         an entry with w = 0 influences nothing but its own returned value.  Two calls agree bit for
+ *                        bit; there are no floating-point atomics.  The result of injecting trial j does not depend on
+ *                        n_trial, on j's position or on the other trials.  raw and the exposure table's data are never
+ *                        written
+ *   no pixel             n_pix = 0: every component ends; U is zeros behind the column of ones, nothing else is written */
+
+/* Make the raw exposures resident (the host array is read during the call only).  PROM_E_STATE without a resident
+ * exposure table; PROM_E_ARG when n_exp or n_pix differs from the table's or n_exp > 4096.  prom_expose_set, and
+ * whatever drops the exposure table, drops them (the calls below then fail with PROM_E_STATE). */
+int32_t prom_sysrem_set(prom_ctx* ctx, int32_t n_exp, int32_t n_pix, const double* raw);
+/* SYSREM of the raw exposures without an injection.  Each output may be NULL: U_out[n_exp][n_comp + ones],
+ * cleaned_out[n_exp][n_pix], injected_out[n_exp][n_pix].  highpass and ones are 0 or 1; PROM_E_ARG for a broken range;
+ * PROM_E_STATE without resident raw exposures and with highpass = 1 without a resident high-pass. */
+int32_t prom_sysrem_clean(prom_ctx* ctx, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out,
+                          double* cleaned_out, double* injected_out);
+/* The same after injecting trial `trial` of the last run's R (its broadened R_b while that is current) at `scale`, on
+ * the run's stream.  PROM_E_ARG also for a trial outside [0, n_trial) and a scale that is not finite; PROM_E_STATE also
+ * without a completed run or when the table has another n_orb. */
+int32_t prom_transit_inject(prom_ctx* ctx, int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter,
+                            int32_t ones, double* U_out, double* cleaned_out, double* injected_out);
+/* The same for a spectrum the caller supplies (the checks of prom_spectrum_expose). */
+int32_t prom_spectrum_inject(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                             int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones,
+                             double* U_out, double* cleaned_out, double* injected_out);
+/* Measurement aid (tools/sysrem_bench.py), not for callers: mean device durations in milliseconds over n_runs
+ * repetitions of the last clean or inject call: ms_out[0] the SYSREM loop (weights, every fit, the cleaned data),
+ * ms_out[1] the injection (the one-trial model and D; NaN for a clean call), ms_out[2] k_highpass (NaN without it).
+ * PROM_E_STATE when there is no such call. */
+int32_t prom_sysrem_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
+
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop
  * events on its own dispatch packet (groups of kernels: the first start to the last stop).  ms_out[k] is

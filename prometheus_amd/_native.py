@@ -156,6 +156,13 @@ SIGNATURES = {
     "prom_transit_broaden": (C.c_int32, [C.c_void_p]),
     "prom_transit_broadened": (C.c_int32, [C.c_void_p, _dp]),
     "prom_broaden_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
+    "prom_sysrem_set": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp]),
+    "prom_sysrem_clean": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "prom_transit_inject": (C.c_int32, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        _dp, _dp, _dp]),
+    "prom_spectrum_inject": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, C.c_double, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "prom_sysrem_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -284,6 +291,7 @@ class Device:
         self._od_key = None
         self._od_n_seg = 0
         self._br_key = None
+        self._sy_key = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -416,6 +424,7 @@ class Device:
             self._dt_key = None                      # ... with its filter
             self._hp_key = None                      # ... and its high-pass
             self._od_key = None                      # ... and its orders
+            self._sy_key = None                      # ... and its raw exposures
         self._n_atoms = prob.n_atoms
         self._n_pr = prob.struct.n_pr
 
@@ -497,6 +506,7 @@ class Device:
         self._dt_key = None                    # ... with its filter
         self._hp_key = None                    # ... and its high-pass
         self._od_key = None                    # ... and its orders
+        self._sy_key = None                    # ... and its raw exposures
         self._check(self.lib.prom_observe_set(self.h, n_pix, _d(lam), _d(sig), float(k), n_orb,
                                               _d(f) if f is not None else None,
                                               _d(data) if data is not None else None,
@@ -617,6 +627,7 @@ class Device:
         self._dt_key = None   # the library drops the filter with the table it was set for
         self._hp_key = None   # ... and the high-pass
         self._od_key = None   # ... and the orders
+        self._sy_key = None   # ... and the raw exposures of the injections
         self._check(self.lib.prom_expose_set(self.h, n_exp, F.shape[1], n_tap, rows.ctypes.data_as(C.POINTER(C.c_int32)),
                                              _d(a), _d(F), _d(data), _d(ivar)), "prom_expose_set")
         self._ex_shape = (n_exp, F.shape[1], n_pix)
@@ -867,6 +878,67 @@ class Device:
         ms = C.c_double(0.0)
         self._check(self.lib.prom_broaden_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_broaden_kernel_ms")
         return float(ms.value)
+
+    # ---- injection and SYSREM (prom_hip.h "injection and SYSREM on the device") -----------------
+    def sysrem_set(self, raw, key=None) -> None:
+        """prom_sysrem_set: the raw exposures raw [n_exp][n_pix] of the resident exposure table, in the device's pixel
+        order (any value; NaN marks a bad pixel).  ``key``: any value the caller keeps in ``sysrem_key`` to skip a
+        later upload of the same data."""
+        raw = _f64(raw)
+        if raw.ndim != 2:
+            raise ValueError("sysrem_set: raw must be [n_exp][n_pix]")
+        self._sy_key = None
+        self._check(self.lib.prom_sysrem_set(self.h, raw.shape[0], raw.shape[1], _d(raw)), "prom_sysrem_set")
+        self._sy_key = key
+
+    @property
+    def sysrem_key(self):
+        """The ``key`` of the raw exposures resident on the context (None: none, or set without a key)."""
+        return self._sy_key
+
+    def _sysrem_outputs(self, n_comp: int, ones: bool, injected: bool):
+        n_exp, _, n_pix = self._ex_shape or (0, 0, 0)
+        U = np.zeros((n_exp, max(int(n_comp) + int(bool(ones)), 0)))
+        cleaned = np.full((n_exp, n_pix), np.nan)
+        inj = np.full((n_exp, n_pix), np.nan) if injected else None
+        return (U, cleaned, inj), (_d(U), _d(cleaned), _d(inj) if injected else None)
+
+    def sysrem_clean(self, n_comp: int, n_iter: int = 30, ones: bool = False, highpass: bool = False,
+                     injected: bool = False):
+        """prom_sysrem_clean: SYSREM of the resident raw exposures, after the resident high-pass with ``highpass``:
+        (U [n_exp][n_comp + ones], cleaned [n_exp][n_pix], injected [n_exp][n_pix] or None), device pixel order."""
+        out, ptr = self._sysrem_outputs(n_comp, ones, injected)
+        self._check(self.lib.prom_sysrem_clean(self.h, int(bool(highpass)), int(n_comp), int(n_iter), int(bool(ones)),
+                                               *ptr), "prom_sysrem_clean")
+        return out
+
+    def transit_inject(self, trial: int, scale: float, n_comp: int, n_iter: int = 30, ones: bool = False,
+                       highpass: bool = False, injected: bool = False):
+        """prom_transit_inject: the same after multiplying trial ``trial`` of the last run's model into the raw
+        exposures at ``scale``."""
+        out, ptr = self._sysrem_outputs(n_comp, ones, injected)
+        self._check(self.lib.prom_transit_inject(self.h, int(trial), float(scale), int(bool(highpass)), int(n_comp),
+                                                 int(n_iter), int(bool(ones)), *ptr), "prom_transit_inject")
+        return out
+
+    def spectrum_inject(self, wav, R, trial: int, scale: float, n_comp: int, n_iter: int = 30, ones: bool = False,
+                        highpass: bool = False, injected: bool = False):
+        """prom_spectrum_inject: the same for R[n_orb][n_wav] on the ascending grid wav."""
+        wav, R = _f64(wav), _f64(R)
+        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
+            raise ValueError("spectrum_inject: R must be [n_orb][n_wav]")
+        out, ptr = self._sysrem_outputs(n_comp, ones, injected)
+        self._check(self.lib.prom_spectrum_inject(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(trial), float(scale),
+                                                  int(bool(highpass)), int(n_comp), int(n_iter), int(bool(ones)), *ptr),
+                    "prom_spectrum_inject")
+        return out
+
+    def sysrem_kernel_ms(self, n_runs: int = 5):
+        """prom_sysrem_kernel_ms: mean device durations [ms] of (the SYSREM loop, the injection, k_highpass) for the
+        last clean or inject call; NaN for a stage that call did not have."""
+        ms = (C.c_double * 3)(0.0, 0.0, 0.0)
+        self._check(self.lib.prom_sysrem_kernel_ms(self.h, int(n_runs), ms), "prom_sysrem_kernel_ms")
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     # ---- stellar disk -----------------------------------------------------------------------
     def star_disk_flux(self, table_id: int, shift, clv, rho, dphi: float, drho: float, wavelength) -> np.ndarray:

@@ -17,6 +17,7 @@
 #include "highpass_index.h"
 #include "order_index.h"
 #include "broaden_index.h"
+#include "sysrem_index.h"
 
 using prom::DevBuf;
 using prom::Error;
@@ -2118,6 +2119,8 @@ int32_t prom_expose_set(prom_ctx* ctx, int32_t n_exp, int32_t n_trial, int32_t n
     ex.dt_set = ex.dt_ran = false;   // a filter belongs to the table it was set for
     ex.hp_set = ex.hp_ran = false;   // ... and so does a high-pass
     ex.od_set = ex.od_ran = false;   // ... and the orders of the per-order moments
+    ctx->sy.set = false;             // ... and the raw exposures of the injections
+    ctx->sy.last_source = 0;
     ex.last_wav = ex.last_R = nullptr;
     PROM_REQUIRE(n_exp >= 1 && n_exp <= 65535 && n_trial >= 1 && n_trial <= (1 << 24) && n_tap >= 1 &&
                      n_tap <= (1 << 16) && row && a && F,
@@ -2933,6 +2936,207 @@ int32_t prom_broaden_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
       sum += ms;
     }
     *ms_out = sum / n_runs;
+  });
+}
+
+// ------------------------------------------------------------------------------ injection and SYSREM
+int32_t prom_sysrem_set(prom_ctx* ctx, int32_t n_exp, int32_t n_pix, const double* raw) {
+  return guarded(ctx, [&] {
+    prom::SyDev& sy = ctx->sy;
+    sy.set = false;
+    sy.last_source = 0;
+    if (!ctx->ex.set || !ctx->obs.set || ctx->obs.n_orb != ctx->ex.n_orb)
+      throw Error(PROM_E_STATE, "prom_sysrem_set: no exposure table on the context (prom_expose_set)");
+    PROM_REQUIRE(n_exp == ctx->ex.n_exp && n_pix == ctx->obs.n_pix,
+                 "prom_sysrem_set: raw must be [n_exp][n_pix] of the exposure table");
+    PROM_REQUIRE(n_exp <= prom::kSyMaxExp, "prom_sysrem_set: more than 4096 exposures");
+    const int64_t n = (int64_t)n_exp * n_pix;
+    PROM_REQUIRE(n == 0 || raw, "prom_sysrem_set: raw missing");
+    const hipStream_t st = ctx->stream;
+    upload(sy.raw, raw, n, st);
+    PROM_HIP(hipStreamSynchronize(st));   // the host array is read during the call only
+    sy.n_exp = n_exp;
+    sy.n_pix = n_pix;
+    sy.set = true;
+  });
+}
+
+namespace {
+
+// what a clean / inject call asks for (source 1: clean, 2: the last run's R, 3: a caller's spectrum)
+struct SyCall {
+  int32_t source, trial, highpass, n_comp, n_iter, ones;
+  double scale;
+};
+
+void sysrem_check(prom_ctx* ctx, const char* who, const SyCall& c) {
+  const std::string w(who);
+  if (!ctx->ex.set || !ctx->obs.set || ctx->obs.n_orb != ctx->ex.n_orb)
+    throw Error(PROM_E_STATE, w + ": no exposure table on the context (prom_expose_set; a later prom_observe_set or a "
+                                  "prom_transit_set with another n_orb drops it)");
+  if (!ctx->sy.set)
+    throw Error(PROM_E_STATE, w + ": no raw exposures on the context (prom_sysrem_set; a later prom_expose_set, or "
+                                  "whatever drops the exposure table, drops them)");
+  if (c.highpass != 0 && c.highpass != 1) throw Error(PROM_E_ARG, w + ": highpass must be 0 or 1");
+  if (c.ones != 0 && c.ones != 1) throw Error(PROM_E_ARG, w + ": ones must be 0 or 1");
+  if (c.n_comp < 0 || c.n_comp + c.ones < 1 || c.n_comp + c.ones > prom::kSyMaxComp)
+    throw Error(PROM_E_ARG, w + ": n_comp >= 0 and 1 <= n_comp + ones <= 16");
+  if (c.n_iter < 1) throw Error(PROM_E_ARG, w + ": n_iter must be >= 1");
+  if (c.source != 1) {
+    if (c.trial < 0 || c.trial >= ctx->ex.n_trial) throw Error(PROM_E_ARG, w + ": trial outside [0, n_trial)");
+    if (!std::isfinite(c.scale)) throw Error(PROM_E_ARG, w + ": scale must be finite");
+  }
+  if (c.highpass && !ctx->ex.hp_set)
+    throw Error(PROM_E_STATE, w + ": highpass = 1 without a high-pass on the context (prom_highpass_set)");
+}
+
+// the shared tail of the clean / inject calls on stream st (ev: six events around the injection, the high-pass and
+// SYSREM, and the call runs even without an output)
+void sysrem_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, const SyCall& c,
+               double* U_out, double* cleaned_out, double* injected_out, hipEvent_t* ev) {
+  prom::SyDev& sy = ctx->sy;
+  prom::ExDev& ex = ctx->ex;
+  const prom::ObsDev& ob = ctx->obs;
+  const int32_t n_exp = sy.n_exp, n_pix = sy.n_pix, n_cols = c.n_comp + c.ones;
+  const int64_t n = (int64_t)n_exp * n_pix;
+  if (n_pix == 0) {   // no pixel: every component ends at once
+    if (U_out)
+      for (int32_t e = 0; e < n_exp; ++e)
+        for (int32_t k = 0; k < n_cols; ++k) U_out[prom::sy_u(e, k, n_cols)] = (c.ones && k == 0) ? 1.0 : 0.0;
+    return;
+  }
+  if (!ev && !U_out && !cleaned_out && !injected_out) return;
+  if (c.highpass && prom::hp_workgroups(n_exp, ex.hp_n_seg) > (((int64_t)1 << 31) - 1))   // (before anything is launched)
+    throw Error(PROM_E_ARG, "k_highpass: n_exp n_seg too large for one launch");
+  const int64_t pitch = prom::sy_pitch(n_pix);
+  sy.D.ensure(sizeof(double) * (size_t)n);
+  sy.out.ensure(sizeof(double) * (size_t)n);
+  sy.r.ensure(sizeof(double) * (size_t)(n_exp * pitch));
+  sy.w.ensure(sizeof(double) * (size_t)(n_exp * pitch));
+  sy.a.ensure(sizeof(double) * (size_t)n_exp);
+  sy.ended.ensure(sizeof(int32_t) * (prom::kSyMaxComp + 1));
+  sy.part.ensure(2 * sizeof(double) * (size_t)n_exp * prom::sy_tiles(n_pix));
+  sy.U.ensure(sizeof(double) * (size_t)n_exp * n_cols);
+  if (ev) PROM_HIP(hipEventRecord(ev[0], st));
+  if (c.source != 1) {
+    // the model of trial `trial` alone: its factors as a table of one trial, through k_expose unchanged
+    const double nan = std::nan("");
+    sy.q.ensure(sizeof(double) * (size_t)n_wav);
+    sy.Fj.ensure(sizeof(double) * (size_t)n_exp * ex.n_tap);
+    sy.model.ensure(sizeof(double) * (size_t)n);
+    sy.epart.ensure(sizeof(double) * (size_t)prom::vm_part_doubles(n_exp, 1, prom::vm_chunks(n_pix)));
+    prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, sy.q.as<double>());
+    prom::launch_sysrem_gather(st, ex.F.as<double>(), sy.Fj.as<double>(), n_exp, ex.n_trial, ex.n_tap, c.trial);
+    prom::launch_expose(st, wav, sy.q.as<double>(), R, (int32_t)n_wav, ob.lam.as<double>(), ob.sig.as<double>(), ob.k,
+                        ex.row.as<int32_t>(), ex.a.as<double>(), sy.Fj.as<double>(), ex.data.as<double>(),
+                        ex.ivar.as<double>(), n_pix, n_exp, 1, ex.n_tap, 0, 1, sy.epart.as<double>(),
+                        sy.model.as<double>(), nullptr, nullptr);
+    prom::launch_inject(st, sy.raw.as<double>(), sy.model.as<double>(), c.scale, sy.D.as<double>(), n);
+  } else {
+    PROM_HIP(hipMemcpyAsync(sy.D.p, sy.raw.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+  }
+  if (ev) PROM_HIP(hipEventRecord(ev[1], st));
+  if (ev) PROM_HIP(hipEventRecord(ev[2], st));
+  if (c.highpass)
+    prom::launch_highpass(st, sy.D.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(), ex.hp_g.as<double>(),
+                          ex.hp_half, ex.hp_den, ex.hp_mode, n_exp, ex.hp_n_seg, n_pix, nullptr, nullptr);
+  if (ev) PROM_HIP(hipEventRecord(ev[3], st));
+  if (ev) PROM_HIP(hipEventRecord(ev[4], st));
+  prom::launch_sysrem(st, sy.D.as<double>(), ex.ivar.as<double>(), sy.r.as<double>(), sy.w.as<double>(),
+                      sy.a.as<double>(), sy.ended.as<int32_t>(), sy.part.as<double>(), sy.U.as<double>(),
+                      sy.out.as<double>(), n_exp, n_pix, c.n_comp, c.n_iter, c.ones);
+  if (ev) PROM_HIP(hipEventRecord(ev[5], st));
+  sy.last_source = c.source;
+  sy.last_trial = c.trial;
+  sy.last_scale = c.scale;
+  sy.last_highpass = c.highpass;
+  sy.last_n_comp = c.n_comp;
+  sy.last_n_iter = c.n_iter;
+  sy.last_ones = c.ones;
+  sy.last_n_wav = n_wav;
+  if (U_out) download(U_out, sy.U, (int64_t)n_exp * n_cols, st);
+  if (cleaned_out) download(cleaned_out, sy.out, n, st);
+  if (injected_out) download(injected_out, sy.D, n, st);
+  PROM_HIP(hipStreamSynchronize(st));
+}
+
+}  // namespace
+
+int32_t prom_sysrem_clean(prom_ctx* ctx, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out,
+                          double* cleaned_out, double* injected_out) {
+  return guarded(ctx, [&] {
+    const SyCall c{1, 0, highpass, n_comp, n_iter, ones, 0.0};
+    sysrem_check(ctx, "prom_sysrem_clean", c);
+    sysrem_on(ctx, ctx->stream, nullptr, nullptr, 0, c, U_out, cleaned_out, injected_out, nullptr);
+  });
+}
+
+int32_t prom_transit_inject(prom_ctx* ctx, int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter,
+                            int32_t ones, double* U_out, double* cleaned_out, double* injected_out) {
+  return guarded(ctx, [&] {
+    prom::TransitDev& tr = ctx->tr;
+    const SyCall c{2, trial, highpass, n_comp, n_iter, ones, scale};
+    sysrem_check(ctx, "prom_transit_inject", c);
+    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_inject: no completed run");
+    if (ctx->ex.n_orb != tr.n_orb)
+      throw Error(PROM_E_STATE, "prom_transit_inject: the exposure table has another n_orb");
+    // the last run's stream orders the injection after it
+    sysrem_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, c, U_out, cleaned_out,
+              injected_out, nullptr);
+  });
+}
+
+int32_t prom_spectrum_inject(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                             int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones,
+                             double* U_out, double* cleaned_out, double* injected_out) {
+  return guarded(ctx, [&] {
+    prom::SyDev& sy = ctx->sy;
+    const SyCall c{3, trial, highpass, n_comp, n_iter, ones, scale};
+    sysrem_check(ctx, "prom_spectrum_inject", c);
+    PROM_REQUIRE(n_orb == ctx->ex.n_orb, "prom_spectrum_inject: n_orb differs from the observation's");
+    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_inject: bad spectrum");
+    for (int64_t w = 0; w < n_wav; ++w)
+      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
+                   "prom_spectrum_inject: wavelengths must be finite and ascending");
+    const hipStream_t st = ctx->stream;
+    sy.last_source = 0;   // (the uploads may move the buffers the last call read)
+    upload(sy.wav, wav, n_wav, st);
+    upload(sy.R, R, (int64_t)n_orb * n_wav, st);
+    sy.last_n_orb = n_orb;
+    sysrem_on(ctx, st, sy.wav.as<double>(), sy.R.as<double>(), n_wav, c, U_out, cleaned_out, injected_out, nullptr);
+  });
+}
+
+int32_t prom_sysrem_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
+  return guarded(ctx, [&] {
+    prom::SyDev& sy = ctx->sy;
+    prom::TransitDev& tr = ctx->tr;
+    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_sysrem_kernel_ms: bad arguments");
+    const bool table = ctx->ex.set && ctx->obs.set && ctx->obs.n_orb == ctx->ex.n_orb && sy.set && sy.n_pix > 0;
+    if (!table || sy.last_source == 0 || (sy.last_highpass && !ctx->ex.hp_set) ||
+        (sy.last_source == 2 && (!tr.ran || ctx->ex.n_orb != tr.n_orb || tr.n_wav != sy.last_n_wav)) ||
+        (sy.last_source == 3 && sy.last_n_orb != ctx->ex.n_orb))
+      throw Error(PROM_E_STATE, "prom_sysrem_kernel_ms: no clean or inject call to repeat");
+    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
+    const hipStream_t st = ctx->stream;
+    const SyCall c{sy.last_source, sy.last_trial, sy.last_highpass, sy.last_n_comp, sy.last_n_iter, sy.last_ones,
+                   sy.last_scale};
+    const double* wav = c.source == 2 ? tr.wav.as<double>() : sy.wav.as<double>();
+    const double* R = c.source == 2 ? transit_R(ctx) : sy.R.as<double>();
+    double sum[3] = {0.0, 0.0, 0.0};
+    for (int32_t r = 0; r < n_runs; ++r) {
+      sysrem_on(ctx, st, wav, R, sy.last_n_wav, c, nullptr, nullptr, nullptr, ctx->ev);
+      float ms = 0.0f;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
+      sum[0] += ms;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      sum[1] += ms;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+      sum[2] += ms;
+    }
+    ms_out[0] = sum[0] / n_runs;
+    ms_out[1] = c.source != 1 ? sum[1] / n_runs : std::nan("");
+    ms_out[2] = c.highpass ? sum[2] / n_runs : std::nan("");
   });
 }
 

@@ -497,6 +497,24 @@ struct BrDev {
   int32_t last_n_wav = 0, last_n_orb = 0;
 };
 
+// The raw exposures resident on a context (prom_sysrem_set) and the work buffers of the clean / inject calls.  They
+// belong to the exposure table they were set for: prom_expose_set clears `set`.
+struct SyDev {
+  bool set = false;
+  int32_t n_exp = 0, n_pix = 0;
+  DevBuf raw;                             // [n_exp][n_pix], never written after the upload
+  DevBuf D, out;                          // [n_exp][n_pix]: injected (and high-passed) data, cleaned data
+  DevBuf r, w;                            // [n_exp][sy_pitch(n_pix)]: residuals and weights
+  DevBuf a, ended, part, U;               // [n_exp], int32 [kSyMaxComp + 1], [n_exp][tiles] {num, den}, [n_exp][cols]
+  DevBuf Fj, model, q, epart;             // one trial: factors [n_exp][n_tap], model [n_exp][n_pix], q [n_wav], k_expose's records
+  DevBuf wav, R;                          // prom_spectrum_inject's copies of the caller's spectrum
+  // the last call, for prom_sysrem_kernel_ms to repeat (source 0: none yet, 1: clean, 2: transit, 3: spectrum)
+  int32_t last_source = 0, last_trial = 0, last_highpass = 0, last_n_comp = 0, last_n_iter = 0, last_ones = 0;
+  int32_t last_n_orb = 0;
+  int64_t last_n_wav = 0;
+  double last_scale = 0.0;
+};
+
 }  // namespace prom
 
 struct prom_ctx {
@@ -513,6 +531,7 @@ struct prom_ctx {
   prom::VmDev vm;
   prom::ExDev ex;
   prom::BrDev br;
+  prom::SyDev sy;
   int64_t vmap_scratch_bytes = (int64_t)256 << 20;   // PROM_VMAP_SCRATCH_MB: cap of k_vmap's partial records
   prom::DevBuf scratch[6];
   bool timing = false;
@@ -648,6 +667,15 @@ struct BrRec;
 struct BrKern;
 void launch_broaden(hipStream_t s, const double* wav, const double* q, const double* R, int32_t n_wav, int32_t n_orb,
                     const BrRec* rec, const BrKern& kern, double* Rb, hipEvent_t ev0, hipEvent_t ev1);
+// injection and SYSREM (prom_sysrem.hip): one trial's factors out of F[n_exp][n_trial][n_tap]; D from raw and the
+// one-trial model; the whole of SYSREM on D[n_exp][n_pix] with the work buffers r, w (pitched), a, ended, part:
+// U[n_exp][n_comp + ones] and out[n_exp][n_pix], nothing waits
+void launch_sysrem_gather(hipStream_t s, const double* F, double* Fj, int32_t n_exp, int32_t n_trial, int32_t n_tap,
+                          int32_t j);
+void launch_inject(hipStream_t s, const double* raw, const double* model, double scale, double* D, int64_t n);
+void launch_sysrem(hipStream_t s, const double* D, const double* ivar, double* r, double* w, double* a, int32_t* ended,
+                   double* part, double* U, double* out, int32_t n_exp, int32_t n_pix, int32_t n_comp, int32_t n_iter,
+                   int32_t ones);
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

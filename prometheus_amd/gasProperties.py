@@ -727,6 +727,46 @@ class _ExposeJob:
         self.moments, self.n_used, self.model = part
 
 
+class _InjectJob:
+    """One Transit.clean / Transit.inject call: the pixels, the exposure table, the high-pass and the raw exposures go
+    to the device once each while their content keys are unchanged; inside _integrate the injection then runs over
+    the (one) chunk's R."""
+
+    def __init__(self, inj, n_orb, trial, scale, n_comp, n_iter, ones, highpass=None, broaden=None,
+                 want_injected=False):
+        self.inj = inj
+        self.table = _ExposeJob(inj.exposures, n_orb, False, highpass=highpass, broaden=broaden)
+        self.br = broaden
+        self.args = dict(n_comp=n_comp, n_iter=n_iter, ones=ones, highpass=highpass is not None,
+                         injected=want_injected)
+        self.trial, self.scale = trial, scale
+        self.whole = False
+        self.U = self.data = self.injected = None
+
+    def upload(self, dev) -> None:
+        self.table.upload(dev)
+        if dev.sysrem_key != self.inj.key:   # (a new table has dropped the raw exposures)
+            dev.sysrem_set(self.inj.raw, key=self.inj.key)
+
+    def clean(self, dev):
+        self.add(dev.sysrem_clean(**self.args))
+
+    def run(self, dev, wavelength, a: int, b: int):
+        if not self.whole:   # (inject refuses such a run before it starts)
+            raise RuntimeError("inject: the run was split into wavelength shards or chunks")
+        if self.br is not None:
+            dev.transit_broaden()
+        return dev.transit_inject(self.trial, self.scale, **self.args)
+
+    def add(self, part) -> None:
+        self.U, self.data, self.injected = part
+
+    def result(self):
+        from . import observation as obs
+        ins = self.inj.exposures.instrument
+        return obs.Cleaned(self.U, ins.unsort(self.data), None if self.injected is None else ins.unsort(self.injected))
+
+
 class _BroadenedJob:
     """One Transit.broadened call inside _integrate: the kernel goes to the device once while its content key is
     unchanged, then R_b of the (one) chunk's R comes back."""
@@ -1121,6 +1161,75 @@ class Transit:
                 vm.by_order = obs.OrderMap(job.order_moments, job.order_n_used, orders.labels, orders.keep)
             vm.order_totals = obs.OrderTotals(job.order_totals)
         return vm
+
+    def clean(self, inj, n_comp: int, n_iter: int = 30, ones: bool = False, highpass=None,
+              devices: Optional[Sequence[int]] = None, return_injected: bool = False):
+        """SYSREM of raw exposures on the device, without a model: ``inj`` is an observation.Injection (the raw data
+        of its exposures).  With ``highpass`` (an observation.HighPass made for the same exposures) the data first go
+        through the high-pass along each order, as observation.high_pass filters them; then ``n_comp`` components of
+        ``n_iter`` alternating least-squares steps each are fitted and subtracted (``ones``: every pixel's weighted
+        mean first, and a leading column of ones in U), with the exposures' inverse variances as weights
+        (include/prom_hip.h, "injection and SYSREM on the device").  Returns an observation.Cleaned: ``U`` for
+        observation.Detrend, ``data`` for observation.Exposures, in the caller's pixel order; with
+        ``return_injected`` also ``injected``, the data before SYSREM.  No transit is run.  One device.  TypeError /
+        ValueError for bad arguments, before a device is touched."""
+        from . import observation as obs
+        n_comp, n_iter, ones = obs._check_sysrem_args("clean", inj, n_comp, n_iter, ones, highpass)
+        devices = [0] if devices is None else list(devices)
+        if len(devices) != 1:
+            raise ValueError("clean: SYSREM runs on one device (%d given)" % len(devices))
+        n_orb = len(self.spatialGrid.constructOrbphaseAxis())
+        job = _InjectJob(inj, n_orb, 0, 0.0, n_comp, n_iter, ones, highpass, None, bool(return_injected))
+        dev = _native.get_device(devices[0])
+        with dev.lock:
+            job.upload(dev)
+            job.clean(dev)
+        return job.result()
+
+    def inject(self, inj, trial: int, scale: float = 1.0, n_comp: int = 6, n_iter: int = 30, ones: bool = False,
+               highpass=None, broaden=None, return_injected: bool = False,
+               devices: Optional[Sequence[int]] = None, max_memory_gb: Optional[float] = None,
+               cull_tau: float = 0.0, options: int = 0):
+        """Run the transit, multiply the model of trial ``trial`` of the exposures' table into the raw exposures of
+        ``inj`` (an observation.Injection) at strength ``scale``, D = raw (1 + scale (M - 1)) with M the exposures'
+        unfiltered model as Transit.expose(return_model=True) gives it (a pixel the model does not cover keeps raw),
+        and clean the result as Transit.clean does, all on the device: the injection-recovery step of a detection.
+        ``broaden``: the model is formed from R convolved with that observation.Broadening, as in Transit.expose.
+        Returns an observation.Cleaned.  The run must be one wavelength shard on one device in one chunk, as for
+        Transit.expose.  TypeError / ValueError for bad arguments, before a device is touched."""
+        from . import observation as obs
+        n_comp, n_iter, ones = obs._check_sysrem_args("inject", inj, n_comp, n_iter, ones, highpass)
+        if broaden is not None and not isinstance(broaden, obs.Broadening):
+            raise TypeError("inject: broaden must be an observation.Broadening")
+        if isinstance(trial, bool) or not isinstance(trial, (int, np.integer)):
+            raise TypeError("inject: trial must be an integer")
+        exposures = inj.exposures
+        if not 0 <= int(trial) < exposures.n_trial:
+            raise ValueError("inject: trial %d lies outside [0, %d)" % (int(trial), exposures.n_trial))
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise TypeError("inject: scale must be a number") from None
+        if not math.isfinite(scale):
+            raise ValueError("inject: scale must be finite")
+        n_orb = len(self.spatialGrid.constructOrbphaseAxis())
+        if int(exposures.rows.max()) >= n_orb or int(exposures.rows.min()) < 0:
+            raise ValueError("inject: a tap reads row %d, the transit has %d phases"
+                             % (int(exposures.rows.max()), n_orb))
+        if not hasattr(self, "wavelength"):
+            self.addWavelength()
+        devices = [0] if devices is None else list(devices)
+        max_memory_gb = 2.0 if max_memory_gb is None else max_memory_gb
+        n_wav, chunk = len(self.wavelength), self._wavelength_chunk(max_memory_gb, n_orb)
+        if len(devices) != 1 or n_wav > chunk:
+            raise ValueError(
+                "inject: the run would be split into %d wavelength shard(s) and chunks of %d wavelengths (the grid "
+                "has %d); a tap's model M = num / den needs the sums of the whole grid.  Give one device and raise "
+                "max_memory_gb until the grid fits one chunk." % (len(devices), chunk, n_wav))
+        job = _InjectJob(inj, n_orb, int(trial), scale, n_comp, n_iter, ones, highpass, broaden,
+                         bool(return_injected))
+        self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
+        return job.result()
 
     def broadened(self, broadening, devices: Optional[Sequence[int]] = None, max_memory_gb: Optional[float] = None,
                   cull_tau: float = 0.0, options: int = 0) -> np.ndarray:

@@ -434,6 +434,67 @@ class Orders:
                                                                     self.keep.astype(np.uint8))
 
 
+class Injection:
+    """The raw exposures of Transit.clean / Transit.inject: ``raw`` [n_exp][n_pix] in the caller's pixel order, the
+    data of ``exposures`` before any cleaning (any value; NaN marks a bad pixel).  A model is multiplied into them, and
+    the high-pass and SYSREM run on them, on the device (include/prom_hip.h, "injection and SYSREM on the device");
+    the exposures' inverse variances are the weights.  Sorting into the device's pixel order and the content key that
+    lets a device skip the upload are computed once here; the array is copied.  TypeError / ValueError for bad
+    arguments."""
+
+    MAX_EXP = 4096
+
+    def __init__(self, exposures: Exposures, raw):
+        from .gasProperties import _content_fingerprint
+        if not isinstance(exposures, Exposures):
+            raise TypeError("Injection: exposures must be an observation.Exposures")
+        try:
+            d = np.array(raw, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise TypeError("Injection: raw must be an array of numbers") from None
+        shape = (exposures.n_exp, exposures.instrument.n_pix)
+        if d.shape != shape:
+            raise ValueError("Injection: raw must be [n_exp][n_pix] = [%d][%d]" % shape)
+        if exposures.n_exp > self.MAX_EXP:
+            raise ValueError("Injection: more than %d exposures" % self.MAX_EXP)
+        self.exposures = exposures
+        self.raw = exposures.instrument.sort(d)                 # what the device sees
+        self.exposures_key = exposures.key
+        self.key = ("injection", exposures.key) + _content_fingerprint(self.raw)
+
+
+class Cleaned:
+    """What Transit.clean / Transit.inject return: ``U`` [n_exp][n_comp + ones], the basis SYSREM found (the input of
+    Detrend), ``data`` [n_exp][n_pix], the cleaned exposures in the caller's pixel order (the input of Exposures;
+    entries without weight as they came), and ``injected`` (None unless asked for): the data after the injection and
+    the high-pass, before SYSREM."""
+
+    def __init__(self, U, data, injected=None):
+        self.U, self.data, self.injected = U, data, injected
+
+
+def _check_sysrem_args(who, inj, n_comp, n_iter, ones, highpass):
+    """The refusals of Transit.clean / Transit.inject that need no device: (n_comp, n_iter, ones) as integers."""
+    if not isinstance(inj, Injection):
+        raise TypeError("%s: inj must be an observation.Injection" % who)
+    if highpass is not None:
+        if not isinstance(highpass, HighPass):
+            raise TypeError("%s: highpass must be an observation.HighPass" % who)
+        if highpass.exposures_key != inj.exposures_key:
+            raise ValueError("%s: the HighPass was made for other exposures (another table, pixels or data)" % who)
+    for name, v in (("n_comp", n_comp), ("n_iter", n_iter)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError("%s: %s must be an integer" % (who, name))
+    if not isinstance(ones, (bool, np.bool_)):
+        raise TypeError("%s: ones must be a bool" % who)
+    n_comp, n_iter, ones = int(n_comp), int(n_iter), bool(ones)
+    if n_comp < 0 or not 1 <= n_comp + ones <= Detrend.MAX_COMP:
+        raise ValueError("%s: n_comp >= 0 and 1 <= n_comp + ones <= %d" % (who, Detrend.MAX_COMP))
+    if n_iter < 1:
+        raise ValueError("%s: n_iter must be >= 1" % who)
+    return n_comp, n_iter, ones
+
+
 MAX_BROADENING_NODES = 1025   # of a velocity kernel (the device's record stage)
 
 
