@@ -744,6 +744,87 @@ int32_t prom_spectrum_inject(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const 
  * PROM_E_STATE when there is no such call. */
 int32_t prom_sysrem_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
 
+/* ---- the filter's weights on the device ---------------------------------------------------------
+ * W of "detrended exposures on the device" formed where the basis and the inverse variances already lie: per pixel p,
+ * W_p = (U^T diag(v_p) U)^-1 U^T diag(v_p), by a Cholesky factorisation of the normal matrix.  All float64.  Every
+ * product, sum, difference, quotient and square root is rounded on its own (fl), there is no fused multiply-add, and
+ * the order of every sum named here is part of the definition; a plain numpy loop gives the same bits
+ * (tests/helpers/filter_ref.py).
+ *
+ *   inputs               U[n_exp][K], finite, 1 <= K <= 16, n_exp >= 1; ivar[n_exp][n_pix], any value
+ *   weights              v_e = ivar[e][p] when that is finite and > 0, else +0; cnt = the number of e with v_e > 0
+ *   normal matrix        only the lower triangle i >= j is formed.  Every N_ij starts at +0; in ascending e an exposure
+ *                        with v_e = 0 is skipped, the others give t = fl(v_e U[e][i]) and
+ *                        N_ij = fl(N_ij + fl(t U[e][j]))
+ *   tolerance            dmax starts at N_00 and takes, in ascending i, every N_ii > dmax;
+ *                        tol = fl(fl(K 2^-52) dmax)
+ *   Cholesky             for j = 0 .. K - 1 in order: s = N_jj, then for k = 0 .. j - 1 ascending
+ *                        s = fl(s - fl(L_jk L_jk)).  The pixel is singular when cnt < K or when s > tol is false for
+ *                        some j (NaN and an infinite dmax therefore count as singular).  L_jj = sqrt(s).  For i > j:
+ *                        s' = N_ij, then for k ascending s' = fl(s' - fl(L_ik L_jk)), and L_ij = fl(s' / L_jj)
+ *   solve                for every e with v_e > 0: forward, y_i = fl((fl(v_e U[e][i]) - sum) / L_ii) where the terms
+ *                        fl(L_ik y_k), k = 0 .. i - 1 ascending, are subtracted one by one, each difference rounded;
+ *                        backward for i = K - 1 .. 0, x_i = fl((y_i - sum) / L_ii) with the terms fl(L_ki x_k),
+ *                        k = K - 1 .. i + 1 descending, subtracted the same way.  W[k][e][p] = x_k
+ *   zeros                W[k][e][p] = +0 exactly for every k when v_e = 0.  A singular pixel has W = +0 throughout,
+ *                        and so has a pixel any of whose x is not finite
+ *   independence         a pixel's W depends on U and on that pixel's column of ivar only: not on n_pix, the pixel's
+ *                        position or the launch.  Two calls agree bit for bit; there are no atomics
+ *
+ * This is the device's own rule.  The host's observation.filter_weights keeps its eigenvalue rule and its bits; on
+ * pixels that are not borderline the two agree to rounding.  A zero column of U (a SYSREM component that ended) makes
+ * N_p singular at every pixel, here exactly as on the host: W is +0 everywhere and the filter passes the model through. */
+
+/* The definition on arrays the caller supplies (no table is needed): W_out[n_comp][n_exp][n_pix] from U[n_exp][n_comp]
+ * and ivar[n_exp][n_pix].  PROM_E_ARG for n_comp outside [1, 16], n_exp < 1, n_pix < 0, a U entry that is not finite
+ * or a missing array; n_pix = 0 writes nothing. */
+int32_t prom_filter_weights(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, int32_t n_pix, const double* U,
+                            const double* ivar, double* W_out);
+/* Make the filter resident exactly as prom_detrend_set would with the W of the definition over the exposure table's
+ * ivar; W is formed on the device and comes back in W_out[n_comp][n_exp][n_pix] unless that is NULL.  The checks and
+ * states are prom_detrend_set's (there is no W to check), and every detrended, high-pass (detrend = 1) and per-order
+ * (detrend = 1) call afterwards behaves as after prom_detrend_set with (U, W). */
+int32_t prom_detrend_build(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, const double* U, double* W_out);
+/* Measurement aid (tools/recover_bench.py), not for callers: ms_out[0] = the mean device duration in milliseconds over
+ * n_runs repetitions of k_filter_weights as the last prom_detrend_build or recover call launched it.  PROM_E_STATE
+ * when there is no such call. */
+int32_t prom_filter_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
+
+/* ---- recovery on the device ---------------------------------------------------------------------
+ * An injection turned into the recovery's moments in one call: three steps on one stream, one wait at the end.
+ *
+ *   1  the steps of the inject call with the same arguments: the cleaned data C[n_exp][n_pix] and
+ *      U[n_exp][n_comp + ones] stay in device memory
+ *   2  W of (U, the table's ivar) by "the filter's weights on the device", in a buffer of the recovery's own: the
+ *      resident filter of prom_detrend_set / prom_detrend_build is neither read nor replaced, and raw and the
+ *      table's data are never written
+ *   3  the whole table's model as the expose calls form it (from R_b while that is current); with highpass = 1 the
+ *      resident high-pass over it; k_detrend with (U, W); the moments with C in the place of the table's data; with
+ *      orders = 1 the per-order records and totals too
+ *
+ *   equivalence          every output equals, bit for bit, what prom_spectrum_expose_detrended, the high-pass call with
+ *                        detrend = 1 or the per-order call with detrend = 1 returns on a table with the same pixels,
+ *                        rows, weights, factors and ivar, with data = C and the filter set to (U, W)
+ *   outputs              mom_out[n_exp][n_trial][7], n_used_out[n_exp][n_trial]; with orders = 1
+ *                        orec_mom_out[n_exp][n_trial][n_seg][7], orec_n_used_out[n_exp][n_trial][n_seg] and
+ *                        tot_out[n_exp][n_trial][4] (untouched with orders = 0); U_out[n_exp][n_comp + ones];
+ *                        model_out[n_exp][n_trial][n_pix].  Any of them may be NULL
+ *   errors               the union of the inject call's and the per-order call's; orders must be 0 or 1, and
+ *                        orders = 1 without resident orders is PROM_E_STATE
+ *   no pixel             n_pix = 0 gives zeros (and the U of the inject call)
+ *   memory               the model of all trials is resident at once, as for the detrended calls: PROM_E_NOMEM with
+ *                        the same remedy */
+int32_t prom_transit_recover(prom_ctx* ctx, int32_t trial, double scale, int32_t highpass, int32_t n_comp,
+                             int32_t n_iter, int32_t ones, int32_t orders, double* mom_out, int64_t* n_used_out,
+                             double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out, double* U_out,
+                             double* model_out);
+/* The same for a spectrum the caller supplies (the checks of prom_spectrum_expose). */
+int32_t prom_spectrum_recover(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                              int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter,
+                              int32_t ones, int32_t orders, double* mom_out, int64_t* n_used_out,
+                              double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out, double* U_out,
+                              double* model_out);
+
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop
  * events on its own dispatch packet (groups of kernels: the first start to the last stop).  ms_out[k] is

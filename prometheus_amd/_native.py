@@ -163,6 +163,15 @@ SIGNATURES = {
     "prom_spectrum_inject": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, C.c_double, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "prom_sysrem_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
+    "prom_filter_weights": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "prom_detrend_build": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]),
+    "prom_filter_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
+    "prom_transit_recover": (C.c_int32, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, _dp, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), _dp, _dp,
+                                         _dp]),
+    "prom_spectrum_recover": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, C.c_double, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.POINTER(C.c_int64), _dp,
+                                          C.POINTER(C.c_int64), _dp, _dp, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -939,6 +948,77 @@ class Device:
         ms = (C.c_double * 3)(0.0, 0.0, 0.0)
         self._check(self.lib.prom_sysrem_kernel_ms(self.h, int(n_runs), ms), "prom_sysrem_kernel_ms")
         return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # ---- the filter's weights and the recovery (prom_hip.h "the filter's weights on the device") ----
+    def filter_weights(self, U, ivar) -> np.ndarray:
+        """prom_filter_weights: W [n_comp][n_exp][n_pix] of U [n_exp][n_comp] (finite, 1 <= n_comp <= 16) and ivar
+        [n_exp][n_pix] (any value), by the device's definition.  No table is needed."""
+        U, ivar = _f64(U), _f64(ivar)
+        if U.ndim != 2 or ivar.ndim != 2 or ivar.shape[0] != U.shape[0]:
+            raise ValueError("filter_weights: U must be [n_exp][n_comp] and ivar [n_exp][n_pix]")
+        n_exp, n_comp = U.shape
+        W = np.zeros((n_comp, n_exp, ivar.shape[1]))
+        self._check(self.lib.prom_filter_weights(self.h, n_exp, n_comp, ivar.shape[1], _d(U), _d(ivar), _d(W)),
+                    "prom_filter_weights")
+        return W
+
+    def detrend_build(self, U, key=None, weights: bool = False):
+        """prom_detrend_build: the filter of the resident exposure table from U [n_exp][n_comp] alone; W is formed on
+        the device over the table's ivar and returned ([n_comp][n_exp][n_pix], device pixel order) with ``weights``.
+        ``key``: as detrend_set's."""
+        U = _f64(U)
+        if U.ndim != 2:
+            raise ValueError("detrend_build: U must be [n_exp][n_comp]")
+        n_exp, n_comp = U.shape
+        n_pix = (self._ex_shape or (0, 0, 0))[2]
+        W = np.zeros((n_comp, n_exp, n_pix)) if weights else None
+        self._dt_key = None
+        self._check(self.lib.prom_detrend_build(self.h, n_exp, n_comp, _d(U), _d(W) if weights else None),
+                    "prom_detrend_build")
+        self._dt_key = key
+        return W
+
+    def filter_kernel_ms(self, n_runs: int = 20) -> float:
+        """prom_filter_kernel_ms: mean device duration [ms] of k_filter_weights for the last build or recover call."""
+        ms = C.c_double(0.0)
+        self._check(self.lib.prom_filter_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_filter_kernel_ms")
+        return float(ms.value)
+
+    def _recover_outputs(self, n_comp: int, ones: bool, orders: bool, moments: bool, records: bool, totals: bool,
+                         model: bool):
+        n_exp = (self._ex_shape or (0, 0, 0))[0]
+        U = np.zeros((n_exp, max(int(n_comp) + int(bool(ones)), 0)))
+        if orders:
+            out, ptr = self._orders_outputs(moments, records, totals, model)
+        else:
+            (mom, nu, mod), p = self._expose_outputs(moments, model)
+            out, ptr = (mom, nu, None, None, None, mod), (p[0], p[1], None, None, None, p[2])
+        return out + (U,), ptr[:5] + (_d(U), ptr[5])
+
+    def transit_recover(self, trial: int, scale: float, n_comp: int, n_iter: int = 30, ones: bool = False,
+                        highpass: bool = False, orders: bool = False, moments: bool = True, records: bool = True,
+                        totals: bool = True, model: bool = False):
+        """prom_transit_recover: trial ``trial`` of the last run's model injected at ``scale``, cleaned, and the whole
+        table's filtered model met with the cleaned data, all on the device: (moments, n_used, order moments, order
+        n_used, totals, final model, U [n_exp][n_comp + ones]); the per-order entries are None without ``orders``."""
+        out, ptr = self._recover_outputs(n_comp, ones, orders, moments, records, totals, model)
+        self._check(self.lib.prom_transit_recover(self.h, int(trial), float(scale), int(bool(highpass)), int(n_comp),
+                                                  int(n_iter), int(bool(ones)), int(bool(orders)), *ptr),
+                    "prom_transit_recover")
+        return out
+
+    def spectrum_recover(self, wav, R, trial: int, scale: float, n_comp: int, n_iter: int = 30, ones: bool = False,
+                         highpass: bool = False, orders: bool = False, moments: bool = True, records: bool = True,
+                         totals: bool = True, model: bool = False):
+        """prom_spectrum_recover: the same for R[n_orb][n_wav] on the ascending grid wav."""
+        wav, R = _f64(wav), _f64(R)
+        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
+            raise ValueError("spectrum_recover: R must be [n_orb][n_wav]")
+        out, ptr = self._recover_outputs(n_comp, ones, orders, moments, records, totals, model)
+        self._check(self.lib.prom_spectrum_recover(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(trial),
+                                                   float(scale), int(bool(highpass)), int(n_comp), int(n_iter),
+                                                   int(bool(ones)), int(bool(orders)), *ptr), "prom_spectrum_recover")
+        return out
 
     # ---- stellar disk -----------------------------------------------------------------------
     def star_disk_flux(self, table_id: int, shift, clv, rho, dphi: float, drho: float, wavelength) -> np.ndarray:

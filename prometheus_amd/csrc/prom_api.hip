@@ -18,6 +18,7 @@
 #include "order_index.h"
 #include "broaden_index.h"
 #include "sysrem_index.h"
+#include "filter_index.h"
 
 using prom::DevBuf;
 using prom::Error;
@@ -2121,6 +2122,7 @@ int32_t prom_expose_set(prom_ctx* ctx, int32_t n_exp, int32_t n_trial, int32_t n
     ex.od_set = ex.od_ran = false;   // ... and the orders of the per-order moments
     ctx->sy.set = false;             // ... and the raw exposures of the injections
     ctx->sy.last_source = 0;
+    ctx->rc.last = 0;
     ex.last_wav = ex.last_R = nullptr;
     PROM_REQUIRE(n_exp >= 1 && n_exp <= 65535 && n_trial >= 1 && n_trial <= (1 << 24) && n_tap >= 1 &&
                      n_tap <= (1 << 16) && row && a && F,
@@ -2272,6 +2274,7 @@ int32_t prom_detrend_set(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, const dou
   return guarded(ctx, [&] {
     prom::ExDev& ex = ctx->ex;
     ex.dt_set = ex.dt_ran = false;
+    if (ctx->rc.last == 1) ctx->rc.last = 0;
     if (!ex.set || !ctx->obs.set || ctx->obs.n_orb != ex.n_orb)
       throw Error(PROM_E_STATE, "prom_detrend_set: no exposure table on the context (prom_expose_set)");
     PROM_REQUIRE(n_exp == ex.n_exp, "prom_detrend_set: n_exp differs from the exposure table's");
@@ -2290,8 +2293,9 @@ int32_t prom_detrend_set(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, const dou
 }
 
 // the moments of the model in ex.model, in batches of whole trial groups (ev: events around the first batch's
-// k_model_moments)
-static void moments_launch(prom_ctx* ctx, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+// k_model_moments; data: what stands in the place of the table's data, the recovery's cleaned exposures)
+static void moments_launch(prom_ctx* ctx, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
+                           const double* data = nullptr) {
   prom::ExDev& ex = ctx->ex;
   const prom::ObsDev& ob = ctx->obs;
   const int32_t n_chunks = prom::vm_chunks(ob.n_pix), n_groups = prom::vm_groups(ex.n_trial);
@@ -2304,7 +2308,7 @@ static void moments_launch(prom_ctx* ctx, hipStream_t st, hipEvent_t ev0, hipEve
                  ex.n_trial, n_groups, (n_groups + bg - 1) / bg, bg, n_chunks);
   for (int32_t g = 0; g < n_groups; g += bg) {
     const int32_t j_first = prom::vm_group_first(g), nb = std::min(nb_max, ex.n_trial - j_first);
-    prom::launch_model_moments(st, ex.model.as<double>(), ex.flag.as<uint8_t>(), ex.data.as<double>(),
+    prom::launch_model_moments(st, ex.model.as<double>(), ex.flag.as<uint8_t>(), data ? data : ex.data.as<double>(),
                                ex.ivar.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, j_first, nb, ex.part.as<double>(),
                                g == 0 ? ev0 : nullptr, g == 0 ? ev1 : nullptr);
     prom::launch_vmap_reduce(st, ex.part.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, j_first, nb, ex.mom.as<double>(),
@@ -2623,9 +2627,9 @@ int32_t prom_orders_set(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32
 
 // k_order_moments + k_order_totals over the final model in ex.model, in batches of whole trial groups under the scratch
 // cap (one group at least); a batch's records go to the caller's arrays when they are wanted (ev: events around the two
-// kernels of the first batch)
+// kernels of the first batch; data: as moments_launch's)
 static void orders_launch(prom_ctx* ctx, hipStream_t st, double* orec_mom_out, int64_t* orec_n_used_out,
-                          hipEvent_t* ev) {
+                          hipEvent_t* ev, const double* data = nullptr) {
   prom::ExDev& ex = ctx->ex;
   const int32_t n_pix = ctx->obs.n_pix, n_seg = ex.od_n_seg, n_groups = prom::od_groups(ex.n_trial);
   const int32_t bg = prom::od_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, n_seg, n_groups);
@@ -2641,7 +2645,7 @@ static void orders_launch(prom_ctx* ctx, hipStream_t st, double* orec_mom_out, i
   if (want) host.resize((size_t)prom::od_record_doubles(ex.n_exp, nb_max, n_seg));
   for (int32_t g = 0; g < n_groups; g += bg) {
     const int32_t j_first = prom::od_group_first(g), nb = std::min(nb_max, ex.n_trial - j_first);
-    prom::launch_order_moments(st, ex.model.as<double>(), ex.flag.as<uint8_t>(), ex.data.as<double>(),
+    prom::launch_order_moments(st, ex.model.as<double>(), ex.flag.as<uint8_t>(), data ? data : ex.data.as<double>(),
                                ex.ivar.as<double>(), ex.od_seg.as<int32_t>(), ex.od_perm.as<int32_t>(), n_pix, ex.n_exp,
                                ex.n_trial, j_first, nb, n_seg, ex.od_rec.as<double>(), ev && g == 0 ? ev[0] : nullptr,
                                ev && g == 0 ? ev[1] : nullptr);
@@ -2991,9 +2995,10 @@ void sysrem_check(prom_ctx* ctx, const char* who, const SyCall& c) {
 }
 
 // the shared tail of the clean / inject calls on stream st (ev: six events around the injection, the high-pass and
-// SYSREM, and the call runs even without an output)
+// SYSREM, and the call runs even without an output; wait = false: a recover call goes on on the same stream, so the call
+// runs whatever the outputs and does not wait)
 void sysrem_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, const SyCall& c,
-               double* U_out, double* cleaned_out, double* injected_out, hipEvent_t* ev) {
+               double* U_out, double* cleaned_out, double* injected_out, hipEvent_t* ev, bool wait = true) {
   prom::SyDev& sy = ctx->sy;
   prom::ExDev& ex = ctx->ex;
   const prom::ObsDev& ob = ctx->obs;
@@ -3005,7 +3010,8 @@ void sysrem_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R
         for (int32_t k = 0; k < n_cols; ++k) U_out[prom::sy_u(e, k, n_cols)] = (c.ones && k == 0) ? 1.0 : 0.0;
     return;
   }
-  if (!ev && !U_out && !cleaned_out && !injected_out) return;
+  if (wait && !ev && !U_out && !cleaned_out && !injected_out) return;
+  if (ctx->rc.last == 2) ctx->rc.last = 0;   // (U may move or change its shape)
   if (c.highpass && prom::hp_workgroups(n_exp, ex.hp_n_seg) > (((int64_t)1 << 31) - 1))   // (before anything is launched)
     throw Error(PROM_E_ARG, "k_highpass: n_exp n_seg too large for one launch");
   const int64_t pitch = prom::sy_pitch(n_pix);
@@ -3057,7 +3063,7 @@ void sysrem_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R
   if (U_out) download(U_out, sy.U, (int64_t)n_exp * n_cols, st);
   if (cleaned_out) download(cleaned_out, sy.out, n, st);
   if (injected_out) download(injected_out, sy.D, n, st);
-  PROM_HIP(hipStreamSynchronize(st));
+  if (wait) PROM_HIP(hipStreamSynchronize(st));
 }
 
 }  // namespace
@@ -3137,6 +3143,207 @@ int32_t prom_sysrem_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
     ms_out[0] = sum[0] / n_runs;
     ms_out[1] = c.source != 1 ? sum[1] / n_runs : std::nan("");
     ms_out[2] = c.highpass ? sum[2] / n_runs : std::nan("");
+  });
+}
+
+// ------------------------------------------------------------------------------ the filter's weights and the recovery
+int32_t prom_filter_weights(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, int32_t n_pix, const double* U,
+                            const double* ivar, double* W_out) {
+  return guarded(ctx, [&] {
+    prom::RcDev& rc = ctx->rc;
+    PROM_REQUIRE(n_comp >= 1 && n_comp <= prom::kDtMaxComp, "prom_filter_weights: n_comp must lie in [1, 16]");
+    PROM_REQUIRE(n_exp >= 1 && n_pix >= 0, "prom_filter_weights: n_exp must be >= 1 and n_pix >= 0");
+    const int64_t nu = (int64_t)n_exp * n_comp, ni = (int64_t)n_exp * n_pix, nw = nu * n_pix;
+    PROM_REQUIRE(U && (n_pix == 0 || (ivar && W_out)), "prom_filter_weights: U, ivar or W_out missing");
+    for (int64_t i = 0; i < nu; ++i) PROM_REQUIRE(obs_finite(U[i]), "prom_filter_weights: U must be finite");
+    if (n_pix == 0) return;
+    const hipStream_t st = ctx->stream;
+    upload(rc.fU, U, nu, st);
+    upload(rc.fivar, ivar, ni, st);
+    rc.fW.ensure(sizeof(double) * (size_t)nw);
+    prom::launch_filter_weights(st, rc.fU.as<double>(), rc.fivar.as<double>(), rc.fW.as<double>(), n_exp, n_comp, n_pix,
+                                nullptr, nullptr);
+    download(W_out, rc.fW, nw, st);
+    PROM_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int32_t prom_detrend_build(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, const double* U, double* W_out) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    ex.dt_set = ex.dt_ran = false;
+    if (ctx->rc.last == 1) ctx->rc.last = 0;
+    if (!ex.set || !ctx->obs.set || ctx->obs.n_orb != ex.n_orb)
+      throw Error(PROM_E_STATE, "prom_detrend_build: no exposure table on the context (prom_expose_set)");
+    PROM_REQUIRE(n_exp == ex.n_exp, "prom_detrend_build: n_exp differs from the exposure table's");
+    PROM_REQUIRE(n_comp >= 1 && n_comp <= prom::kDtMaxComp, "prom_detrend_build: n_comp must lie in [1, 16]");
+    const int32_t n_pix = ctx->obs.n_pix;
+    const int64_t nu = (int64_t)n_exp * n_comp, nw = nu * n_pix;
+    PROM_REQUIRE(U, "prom_detrend_build: U missing");
+    for (int64_t i = 0; i < nu; ++i) PROM_REQUIRE(obs_finite(U[i]), "prom_detrend_build: U must be finite");
+    const hipStream_t st = ctx->stream;
+    upload(ex.U, U, nu, st);
+    ex.W.ensure(sizeof(double) * (size_t)std::max<int64_t>(nw, 1));
+    prom::launch_filter_weights(st, ex.U.as<double>(), ex.ivar.as<double>(), ex.W.as<double>(), n_exp, n_comp, n_pix,
+                                nullptr, nullptr);
+    if (W_out) download(W_out, ex.W, nw, st);
+    PROM_HIP(hipStreamSynchronize(st));   // the host array is read during the call only
+    ex.n_comp = n_comp;
+    ex.dt_set = true;
+    if (n_pix > 0) {
+      ctx->rc.last = 1;
+      ctx->rc.last_n_comp = n_comp;
+    }
+  });
+}
+
+int32_t prom_filter_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
+  return guarded(ctx, [&] {
+    prom::RcDev& rc = ctx->rc;
+    prom::ExDev& ex = ctx->ex;
+    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_filter_kernel_ms: bad arguments");
+    const bool table = ex.set && ctx->obs.set && ctx->obs.n_orb == ex.n_orb && ctx->obs.n_pix > 0;
+    const bool built = rc.last == 1 && ex.dt_set && ex.n_comp == rc.last_n_comp;
+    const bool recovered = rc.last == 2 && ctx->sy.set && ctx->sy.last_source != 0 &&
+                           ctx->sy.last_n_comp + ctx->sy.last_ones == rc.last_n_comp;
+    if (!table || !(built || recovered))
+      throw Error(PROM_E_STATE, "prom_filter_kernel_ms: no build or recover call to repeat");
+    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
+    const hipStream_t st = ctx->stream;
+    // the kernel writes the W it wrote before, from the same inputs: the same bits
+    const double* U = built ? ex.U.as<double>() : ctx->sy.U.as<double>();
+    double* W = built ? ex.W.as<double>() : rc.W.as<double>();
+    double sum = 0.0;
+    for (int32_t r = 0; r < n_runs; ++r) {
+      prom::launch_filter_weights(st, U, ex.ivar.as<double>(), W, ex.n_exp, rc.last_n_comp, ctx->obs.n_pix, ctx->ev[0],
+                                  ctx->ev[1]);
+      PROM_HIP(hipStreamSynchronize(st));
+      float ms = 0.0f;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      sum += ms;
+    }
+    ms_out[0] = sum / n_runs;
+  });
+}
+
+namespace {
+
+void recover_check(prom_ctx* ctx, const char* who, const SyCall& c, int32_t orders) {
+  const std::string w(who);
+  sysrem_check(ctx, who, c);
+  if (orders != 0 && orders != 1) throw Error(PROM_E_ARG, w + ": orders must be 0 or 1");
+  if (orders && !ctx->ex.od_set)
+    throw Error(PROM_E_STATE, w + ": orders = 1 without orders on the context (prom_orders_set)");
+}
+
+// the shared tail of the two recover calls on stream st: the inject call's steps, W of (U, ivar), then the chain of
+// the per-order call (highpass, detrend = 1) with the cleaned data in the place of the table's and (U, W) in the place
+// of the resident filter
+void recover_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, const SyCall& c,
+                int32_t orders, double* mom_out, int64_t* n_used_out, double* orec_mom_out, int64_t* orec_n_used_out,
+                double* tot_out, double* U_out, double* model_out) {
+  prom::ExDev& ex = ctx->ex;
+  prom::SyDev& sy = ctx->sy;
+  prom::RcDev& rc = ctx->rc;
+  const int32_t n_pix = ctx->obs.n_pix, n_exp = ex.n_exp, n_cols = c.n_comp + c.ones;
+  const int32_t n_seg = orders ? ex.od_n_seg : 0;
+  const int64_t n = (int64_t)n_exp * ex.n_trial;
+  if (n_pix == 0) {   // no pixel: the inject call's U, every moment, record and total 0 and no model value
+    sysrem_on(ctx, st, wav, R, n_wav, c, U_out, nullptr, nullptr, nullptr);
+    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
+    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
+    if (orders && orec_mom_out) std::fill(orec_mom_out, orec_mom_out + 7 * n * n_seg, 0.0);
+    if (orders && orec_n_used_out) std::fill(orec_n_used_out, orec_n_used_out + n * n_seg, (int64_t)0);
+    if (orders && tot_out) std::fill(tot_out, tot_out + prom::kOdTotals * n, 0.0);
+    return;
+  }
+  const bool want_orders = orders && (orec_mom_out || orec_n_used_out || tot_out);
+  // (before anything is launched)
+  if (orders && prom::od_workgroups(n_exp, 1, n_seg) > (((int64_t)1 << 31) - 1))
+    throw Error(PROM_E_ARG, "k_order_moments: n_exp n_seg too large for one launch");
+  if (c.highpass && prom::hp_workgroups(n, ex.hp_n_seg) > (((int64_t)1 << 31) - 1))
+    throw Error(PROM_E_ARG, "k_highpass: n_exp n_trial n_seg too large for one launch");
+  if (prom::dt_workgroups(ex.n_trial, n_pix) > (((int64_t)1 << 31) - 1))
+    throw Error(PROM_E_ARG, "k_detrend: n_trial n_pix too large for one launch");
+  const int64_t nm = n * n_pix;
+  ex.q.ensure(sizeof(double) * (size_t)n_wav);
+  try {   // the whole table's model is resident at once: it is not batched
+    ex.model.ensure(sizeof(double) * (size_t)nm);
+  } catch (const Error& err) {
+    throw Error(err.code, std::string(err.what()) + ": the recovery keeps the model of all " +
+                              std::to_string(ex.n_trial) + " trials in device memory; give fewer trials per call");
+  }
+  ex.flag.ensure((size_t)ex.n_trial * n_pix);
+  rc.W.ensure(sizeof(double) * (size_t)n_cols * n_exp * n_pix);
+  // the last calls' q, models and flags go: the aids of the expose calls have nothing to repeat
+  ex.dt_ran = ex.hp_ran = ex.od_ran = false;
+  ex.last_wav = ex.last_R = nullptr;
+  // 1: the inject call's steps; the cleaned data stay in sy.out and U in sy.U
+  sysrem_on(ctx, st, wav, R, n_wav, c, U_out, nullptr, nullptr, nullptr, false);
+  // 2: W of (U, the table's ivar)
+  prom::launch_filter_weights(st, sy.U.as<double>(), ex.ivar.as<double>(), rc.W.as<double>(), n_exp, n_cols, n_pix,
+                              nullptr, nullptr);
+  rc.last = 2;
+  rc.last_n_comp = n_cols;
+  // 3: the final model as orders_on forms it, and the moments against the cleaned data
+  const double nan = std::nan("");
+  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
+  expose_launch(ctx, st, wav, R, (int32_t)n_wav, false, ex.model.as<double>(), nullptr, nullptr);
+  if (c.highpass)
+    prom::launch_highpass(st, ex.model.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(),
+                          ex.hp_g.as<double>(), ex.hp_half, ex.hp_den, ex.hp_mode, n, ex.hp_n_seg, n_pix, nullptr,
+                          nullptr);
+  prom::launch_detrend(st, ex.model.as<double>(), sy.U.as<double>(), rc.W.as<double>(), ex.flag.as<uint8_t>(), n_exp,
+                       n_cols, ex.n_trial, n_pix, nullptr, nullptr);
+  if (mom_out || n_used_out) moments_launch(ctx, st, nullptr, nullptr, sy.out.as<double>());
+  if (want_orders) orders_launch(ctx, st, orec_mom_out, orec_n_used_out, nullptr, sy.out.as<double>());
+  if (mom_out) download(mom_out, ex.mom, 7 * n, st);
+  if (n_used_out) download(n_used_out, ex.n_used, n, st);
+  if (orders && tot_out) download(tot_out, ex.od_tot, prom::kOdTotals * n, st);
+  if (model_out) download(model_out, ex.model, nm, st);
+  PROM_HIP(hipStreamSynchronize(st));
+}
+
+}  // namespace
+
+int32_t prom_transit_recover(prom_ctx* ctx, int32_t trial, double scale, int32_t highpass, int32_t n_comp,
+                             int32_t n_iter, int32_t ones, int32_t orders, double* mom_out, int64_t* n_used_out,
+                             double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out, double* U_out,
+                             double* model_out) {
+  return guarded(ctx, [&] {
+    prom::TransitDev& tr = ctx->tr;
+    const SyCall c{2, trial, highpass, n_comp, n_iter, ones, scale};
+    recover_check(ctx, "prom_transit_recover", c, orders);
+    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_recover: no completed run");
+    if (ctx->ex.n_orb != tr.n_orb)
+      throw Error(PROM_E_STATE, "prom_transit_recover: the exposure table has another n_orb");
+    // the last run's stream orders the recovery after it
+    recover_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, c, orders, mom_out,
+               n_used_out, orec_mom_out, orec_n_used_out, tot_out, U_out, model_out);
+  });
+}
+
+int32_t prom_spectrum_recover(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                              int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter,
+                              int32_t ones, int32_t orders, double* mom_out, int64_t* n_used_out,
+                              double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out, double* U_out,
+                              double* model_out) {
+  return guarded(ctx, [&] {
+    prom::SyDev& sy = ctx->sy;
+    const SyCall c{3, trial, highpass, n_comp, n_iter, ones, scale};
+    recover_check(ctx, "prom_spectrum_recover", c, orders);
+    PROM_REQUIRE(n_orb == ctx->ex.n_orb, "prom_spectrum_recover: n_orb differs from the observation's");
+    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_recover: bad spectrum");
+    for (int64_t w = 0; w < n_wav; ++w)
+      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
+                   "prom_spectrum_recover: wavelengths must be finite and ascending");
+    const hipStream_t st = ctx->stream;
+    sy.last_source = 0;   // (the uploads may move the buffers the last call read)
+    upload(sy.wav, wav, n_wav, st);
+    upload(sy.R, R, (int64_t)n_orb * n_wav, st);
+    sy.last_n_orb = n_orb;
+    recover_on(ctx, st, sy.wav.as<double>(), sy.R.as<double>(), n_wav, c, orders, mom_out, n_used_out, orec_mom_out,
+               orec_n_used_out, tot_out, U_out, model_out);
   });
 }
 

@@ -515,6 +515,15 @@ struct SyDev {
   double last_scale = 0.0;
 };
 
+// The filter's weights on the device: the recovery's own W (prom_*_recover; the resident filter of prom_detrend_set
+// lies in ExDev) and what the last k_filter_weights launch read and wrote, for prom_filter_kernel_ms to repeat.
+struct RcDev {
+  DevBuf W;                               // [n_comp + ones][n_exp][n_pix]
+  DevBuf fU, fivar, fW;                   // prom_filter_weights' copies of the caller's arrays and its W
+  int32_t last = 0;                       // 0: none, 1: prom_detrend_build (ExDev's U, W), 2: a recover call (SyDev's U, W)
+  int32_t last_n_comp = 0;
+};
+
 }  // namespace prom
 
 struct prom_ctx {
@@ -532,6 +541,7 @@ struct prom_ctx {
   prom::ExDev ex;
   prom::BrDev br;
   prom::SyDev sy;
+  prom::RcDev rc;
   int64_t vmap_scratch_bytes = (int64_t)256 << 20;   // PROM_VMAP_SCRATCH_MB: cap of k_vmap's partial records
   prom::DevBuf scratch[6];
   bool timing = false;
@@ -676,6 +686,9 @@ void launch_inject(hipStream_t s, const double* raw, const double* model, double
 void launch_sysrem(hipStream_t s, const double* D, const double* ivar, double* r, double* w, double* a, int32_t* ended,
                    double* part, double* U, double* out, int32_t n_exp, int32_t n_pix, int32_t n_comp, int32_t n_iter,
                    int32_t ones);
+// the filter's weights (prom_filter.hip): W[n_comp][n_exp][n_pix] of U[n_exp][n_comp] and ivar[n_exp][n_pix]
+void launch_filter_weights(hipStream_t s, const double* U, const double* ivar, double* W, int32_t n_exp, int32_t n_comp,
+                           int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1);
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

@@ -701,7 +701,10 @@ class _ExposeJob:
         if dev.expose_key != self.ex.key:
             dev.expose_set(self.ex.rows, self.ex.weights, self.ex.factors, self.ex.data, self.ex.ivar, key=self.ex.key)
         if self.dt is not None and dev.detrend_key != self.dt.key:   # (a new table has dropped the filter)
-            dev.detrend_set(self.dt.U, self.dt.W, key=self.dt.key)
+            if self.dt.on_device:
+                dev.detrend_build(self.dt.U, key=self.dt.key)
+            else:
+                dev.detrend_set(self.dt.U, self.dt.W, key=self.dt.key)
         if self.hp is not None and dev.highpass_key != self.hp.key:   # (likewise)
             dev.highpass_set(self.hp.seg_first, self.hp.perm, self.hp.taps, self.hp.mode_id, key=self.hp.key)
         if self.od is not None and dev.orders_key != self.od.key:   # (likewise)
@@ -765,6 +768,37 @@ class _InjectJob:
         from . import observation as obs
         ins = self.inj.exposures.instrument
         return obs.Cleaned(self.U, ins.unsort(self.data), None if self.injected is None else ins.unsort(self.injected))
+
+
+class _RecoverJob:
+    """One Transit.recover call inside _integrate: what _InjectJob uploads, and the orders; then the injection, the
+    filter's weights and the recovery's moments run over the (one) chunk's R in one call."""
+
+    def __init__(self, inj, n_orb, trial, scale, n_comp, n_iter, ones, highpass=None, broaden=None, orders=None,
+                 order_records=True, want_model=False):
+        self.inj = inj
+        self.table = _ExposeJob(inj.exposures, n_orb, False, highpass=highpass, orders=orders, broaden=broaden)
+        self.br = broaden
+        self.args = dict(n_comp=n_comp, n_iter=n_iter, ones=ones, highpass=highpass is not None,
+                         orders=orders is not None, moments=True, records=order_records, totals=True, model=want_model)
+        self.trial, self.scale = trial, scale
+        self.whole = False
+        self.out = None
+
+    def upload(self, dev) -> None:
+        self.table.upload(dev)
+        if dev.sysrem_key != self.inj.key:   # (a new table has dropped the raw exposures)
+            dev.sysrem_set(self.inj.raw, key=self.inj.key)
+
+    def run(self, dev, wavelength, a: int, b: int):
+        if not self.whole:   # (recover refuses such a run before it starts)
+            raise RuntimeError("recover: the run was split into wavelength shards or chunks")
+        if self.br is not None:
+            dev.transit_broaden()
+        return dev.transit_recover(self.trial, self.scale, **self.args)
+
+    def add(self, part) -> None:
+        self.out = part
 
 
 class _BroadenedJob:
@@ -1230,6 +1264,87 @@ class Transit:
                          bool(return_injected))
         self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
         return job.result()
+
+    def recover(self, inj, trial: int, scale: float = 1.0, n_comp: int = 6, n_iter: int = 30, ones: bool = False,
+                highpass=None, broaden=None, orders=None, order_records: bool = True, return_model: bool = False,
+                devices: Optional[Sequence[int]] = None, max_memory_gb: Optional[float] = None,
+                cull_tau: float = 0.0, options: int = 0):
+        """Injection and recovery in one call on the device: what Transit.inject does with the same arguments, then
+        the filter of the basis SYSREM found (its W formed on the device from U and the exposures' inverse variances,
+        include/prom_hip.h, "the filter's weights on the device"), then what Transit.expose(highpass=, detrend=,
+        orders=) does on exposures whose data are the cleaned data.  Neither the cleaned data nor W cross the bus:
+        per (exposure, trial) the seven moments and n_used come back.  Returns the observation.VelocityMap of
+        Transit.expose, with ``by_order`` and ``order_totals`` when ``orders`` are given, plus ``U``
+        [n_exp][n_comp + ones]; with ``return_model`` its ``model`` holds the final (filtered) model.  ``highpass``
+        and ``orders`` must be made for ``inj.exposures``.  One device and one chunk, as for inject and expose.
+        TypeError / ValueError for bad arguments, before a device is touched."""
+        from . import observation as obs
+        n_comp, n_iter, ones = obs._check_sysrem_args("recover", inj, n_comp, n_iter, ones, highpass)
+        if broaden is not None and not isinstance(broaden, obs.Broadening):
+            raise TypeError("recover: broaden must be an observation.Broadening")
+        if orders is not None:
+            if not isinstance(orders, obs.Orders):
+                raise TypeError("recover: orders must be an observation.Orders")
+            if orders.exposures_key != inj.exposures_key:
+                raise ValueError("recover: the Orders were made for other exposures (another table, pixels or data)")
+        if isinstance(trial, bool) or not isinstance(trial, (int, np.integer)):
+            raise TypeError("recover: trial must be an integer")
+        exposures = inj.exposures
+        if not 0 <= int(trial) < exposures.n_trial:
+            raise ValueError("recover: trial %d lies outside [0, %d)" % (int(trial), exposures.n_trial))
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise TypeError("recover: scale must be a number") from None
+        if not math.isfinite(scale):
+            raise ValueError("recover: scale must be finite")
+        n_orb = len(self.spatialGrid.constructOrbphaseAxis())
+        if int(exposures.rows.max()) >= n_orb or int(exposures.rows.min()) < 0:
+            raise ValueError("recover: a tap reads row %d, the transit has %d phases"
+                             % (int(exposures.rows.max()), n_orb))
+        if not hasattr(self, "wavelength"):
+            self.addWavelength()
+        devices = [0] if devices is None else list(devices)
+        max_memory_gb = 2.0 if max_memory_gb is None else max_memory_gb
+        n_wav, chunk = len(self.wavelength), self._wavelength_chunk(max_memory_gb, n_orb)
+        if len(devices) != 1 or n_wav > chunk:
+            raise ValueError(
+                "recover: the run would be split into %d wavelength shard(s) and chunks of %d wavelengths (the grid "
+                "has %d); a tap's model M = num / den needs the sums of the whole grid.  Give one device and raise "
+                "max_memory_gb until the grid fits one chunk." % (len(devices), chunk, n_wav))
+        job = _RecoverJob(inj, n_orb, int(trial), scale, n_comp, n_iter, ones, highpass, broaden, orders,
+                          bool(order_records), bool(return_model))
+        self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
+        mom, nu, omom, onu, tot, model, U = job.out
+        model = exposures.instrument.unsort(model) if return_model else None
+        vm = obs.VelocityMap(mom, nu, exposures.factors, model=model)
+        if orders is not None:
+            vm.by_order = obs.OrderMap(omom, onu, orders.labels, orders.keep) if order_records else None
+            vm.order_totals = obs.OrderTotals(tot)
+        vm.U = U
+        return vm
+
+    def filter_weights(self, exposures, U, devices: Optional[Sequence[int]] = None) -> np.ndarray:
+        """W[n_comp][n_exp][n_pix] of the basis ``U`` [n_exp][n_comp] under the inverse variances of ``exposures``, as
+        the device forms it (include/prom_hip.h, "the filter's weights on the device"), in the caller's pixel order:
+        what Detrend(on_device=True) and Transit.recover filter with.  For inspection and for tests; no transit is
+        run.  One device.  TypeError / ValueError for bad arguments, before a device is touched."""
+        from . import observation as obs
+        if not isinstance(exposures, obs.Exposures):
+            raise TypeError("filter_weights: exposures must be an observation.Exposures")
+        u = np.asarray(U, dtype=np.float64)
+        if u.ndim != 2 or u.shape[0] != exposures.n_exp or not 1 <= u.shape[1] <= obs.Detrend.MAX_COMP:
+            raise ValueError("filter_weights: U must be [n_exp][n_comp] with n_exp = %d and 1 <= n_comp <= %d"
+                             % (exposures.n_exp, obs.Detrend.MAX_COMP))
+        if not np.all(np.isfinite(u)):
+            raise ValueError("filter_weights: U must be finite")
+        devices = [0] if devices is None else list(devices)
+        if len(devices) != 1:
+            raise ValueError("filter_weights: runs on one device (%d given)" % len(devices))
+        dev = _native.get_device(devices[0])
+        with dev.lock:
+            W = dev.filter_weights(u, exposures.ivar)           # (the exposures' ivar is in the device's order)
+        return exposures.instrument.unsort(W)
 
     def broadened(self, broadening, devices: Optional[Sequence[int]] = None, max_memory_gb: Optional[float] = None,
                   cull_tau: float = 0.0, options: int = 0) -> np.ndarray:

@@ -244,11 +244,16 @@ class Detrend:
     caller's pixel order (None: filter_weights with the exposures' inverse variances).  The model of every trial is
     filtered per pixel column, m' = m - U (W_p m), before it meets the data (include/prom_hip.h, "detrended exposures
     on the device").  Sorting W into the device's pixel order and the content key that lets a device skip the upload
-    are computed once here; the arrays are copied.  ValueError for a bad shape or a non-finite value."""
+    are computed once here; the arrays are copied.  ValueError for a bad shape or a non-finite value.
+
+    With ``on_device`` no W is formed or kept on the host (``W`` is then None, and giving one is a ValueError): the
+    device forms it from U and the exposures' inverse variances when the filter is uploaded (include/prom_hip.h, "the
+    filter's weights on the device"; a Cholesky rule of the device's own, which agrees with filter_weights to
+    rounding on pixels that are not borderline), and the key is made of the exposures' key and U's fingerprint."""
 
     MAX_COMP = 16
 
-    def __init__(self, exposures: Exposures, U, W=None):
+    def __init__(self, exposures: Exposures, U, W=None, on_device: bool = False):
         from .gasProperties import _content_fingerprint
         if not isinstance(exposures, Exposures):
             raise TypeError("Detrend: exposures must be an observation.Exposures")
@@ -261,6 +266,14 @@ class Detrend:
             raise ValueError("Detrend: U must be finite")
         self.U = np.ascontiguousarray(u)
         self.n_exp, self.n_comp = self.U.shape
+        self.on_device = bool(on_device)
+        self.exposures_key = exposures.key
+        if self.on_device:
+            if W is not None:
+                raise ValueError("Detrend: on_device forms W on the device; give no W")
+            self.W = None
+            self.key = ("detrend on device", exposures.key) + _content_fingerprint(self.U)
+            return
         shape = (self.n_comp, self.n_exp, exposures.instrument.n_pix)
         if W is None:
             w = filter_weights(self.U, exposures.ivar)          # (the exposures' ivar is in the device's order)
@@ -272,7 +285,6 @@ class Detrend:
         if not np.all(np.isfinite(w)):
             raise ValueError("Detrend: W must be finite")
         self.W = np.ascontiguousarray(w)                        # what the device sees
-        self.exposures_key = exposures.key
         self.key = ("detrend", exposures.key) + _content_fingerprint(self.U, self.W)
 
 
