@@ -270,6 +270,14 @@ def _f64(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _spectrum(wav, R, who: str):
+    """The arguments of Device.``who``: the grid wav [n_wav] and R [n_orb][n_wav] as contiguous float64 arrays."""
+    wav, R = _f64(wav), _f64(R)
+    if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
+        raise ValueError("%s: R must be [n_orb][n_wav]" % who)
+    return wav, R
+
+
 class Device:
     """One prom_ctx (one GPU).  Not thread-safe; use one Device per host thread."""
 
@@ -555,9 +563,7 @@ class Device:
     def spectrum_observe(self, wav, R, edge_lo: float = np.nan, edge_hi: float = np.nan, partials: bool = True,
                          chi2: bool = False):
         """prom_spectrum_observe of R[n_orb][n_wav] on the ascending grid wav: (num, den, chi2, n_used)."""
-        wav, R = _f64(wav), _f64(R)
-        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
-            raise ValueError("spectrum_observe: R must be [n_orb][n_wav]")
+        wav, R = _spectrum(wav, R, "spectrum_observe")
         out, ptr = self._observe_outputs(partials, chi2)
         self._check(self.lib.prom_spectrum_observe(self.h, R.shape[0], len(wav), _d(wav), _d(R), float(edge_lo),
                                                    float(edge_hi), *ptr), "prom_spectrum_observe")
@@ -602,9 +608,7 @@ class Device:
 
     def spectrum_vmap(self, wav, R):
         """prom_spectrum_vmap of R[n_orb][n_wav] on the ascending grid wav: (moments, n_used)."""
-        wav, R = _f64(wav), _f64(R)
-        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
-            raise ValueError("spectrum_vmap: R must be [n_orb][n_wav]")
+        wav, R = _spectrum(wav, R, "spectrum_vmap")
         mom, nu = self._vmap_outputs()
         self._check(self.lib.prom_spectrum_vmap(self.h, R.shape[0], len(wav), _d(wav), _d(R), _d(mom),
                                                 nu.ctypes.data_as(C.POINTER(C.c_int64))), "prom_spectrum_vmap")
@@ -668,9 +672,7 @@ class Device:
 
     def spectrum_expose(self, wav, R, moments: bool = True, model: bool = False):
         """prom_spectrum_expose of R[n_orb][n_wav] on the ascending grid wav: (moments, n_used, model)."""
-        wav, R = _f64(wav), _f64(R)
-        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
-            raise ValueError("spectrum_expose: R must be [n_orb][n_wav]")
+        wav, R = _spectrum(wav, R, "spectrum_expose")
         out, ptr = self._expose_outputs(moments, model)
         self._check(self.lib.prom_spectrum_expose(self.h, R.shape[0], len(wav), _d(wav), _d(R), *ptr),
                     "prom_spectrum_expose")
@@ -712,9 +714,7 @@ class Device:
 
     def spectrum_expose_detrended(self, wav, R, moments: bool = True, model: bool = False):
         """prom_spectrum_expose_detrended of R[n_orb][n_wav] on the ascending grid wav: (moments, n_used, model)."""
-        wav, R = _f64(wav), _f64(R)
-        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
-            raise ValueError("spectrum_expose_detrended: R must be [n_orb][n_wav]")
+        wav, R = _spectrum(wav, R, "spectrum_expose_detrended")
         out, ptr = self._expose_outputs(moments, model)
         self._check(self.lib.prom_spectrum_expose_detrended(self.h, R.shape[0], len(wav), _d(wav), _d(R), *ptr),
                     "prom_spectrum_expose_detrended")
@@ -760,9 +760,7 @@ class Device:
 
     def spectrum_expose_highpass(self, wav, R, detrend: bool = False, moments: bool = True, model: bool = False):
         """prom_spectrum_expose_highpass of R[n_orb][n_wav] on the ascending grid wav: (moments, n_used, model)."""
-        wav, R = _f64(wav), _f64(R)
-        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
-            raise ValueError("spectrum_expose_highpass: R must be [n_orb][n_wav]")
+        wav, R = _spectrum(wav, R, "spectrum_expose_highpass")
         out, ptr = self._expose_outputs(moments, model)
         self._check(self.lib.prom_spectrum_expose_highpass(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(detrend),
                                                            *ptr), "prom_spectrum_expose_highpass")
@@ -824,9 +822,7 @@ class Device:
     def spectrum_expose_orders(self, wav, R, highpass: bool = False, detrend: bool = False, moments: bool = True,
                                records: bool = True, totals: bool = True, model: bool = False):
         """prom_spectrum_expose_orders of R[n_orb][n_wav] on the ascending grid wav: transit_expose_orders' tuple."""
-        wav, R = _f64(wav), _f64(R)
-        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
-            raise ValueError("spectrum_expose_orders: R must be [n_orb][n_wav]")
+        wav, R = _spectrum(wav, R, "spectrum_expose_orders")
         out, ptr = self._orders_outputs(moments, records, totals, model)
         self._check(self.lib.prom_spectrum_expose_orders(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(highpass),
                                                          int(detrend), *ptr), "prom_spectrum_expose_orders")
@@ -863,9 +859,7 @@ class Device:
 
     def spectrum_broaden(self, wav, R) -> np.ndarray:
         """prom_spectrum_broaden of R[n_orb][n_wav] on the ascending, positive grid wav: R_b[n_orb][n_wav]."""
-        wav, R = _f64(wav), _f64(R)
-        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
-            raise ValueError("spectrum_broaden: R must be [n_orb][n_wav]")
+        wav, R = _spectrum(wav, R, "spectrum_broaden")
         out = np.empty(R.shape)
         self._check(self.lib.prom_spectrum_broaden(self.h, R.shape[0], len(wav), _d(wav), _d(R), _d(out)),
                     "prom_spectrum_broaden")
@@ -933,9 +927,7 @@ class Device:
     def spectrum_inject(self, wav, R, trial: int, scale: float, n_comp: int, n_iter: int = 30, ones: bool = False,
                         highpass: bool = False, injected: bool = False):
         """prom_spectrum_inject: the same for R[n_orb][n_wav] on the ascending grid wav."""
-        wav, R = _f64(wav), _f64(R)
-        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
-            raise ValueError("spectrum_inject: R must be [n_orb][n_wav]")
+        wav, R = _spectrum(wav, R, "spectrum_inject")
         out, ptr = self._sysrem_outputs(n_comp, ones, injected)
         self._check(self.lib.prom_spectrum_inject(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(trial), float(scale),
                                                   int(bool(highpass)), int(n_comp), int(n_iter), int(bool(ones)), *ptr),
@@ -1011,9 +1003,7 @@ class Device:
                          highpass: bool = False, orders: bool = False, moments: bool = True, records: bool = True,
                          totals: bool = True, model: bool = False):
         """prom_spectrum_recover: the same for R[n_orb][n_wav] on the ascending grid wav."""
-        wav, R = _f64(wav), _f64(R)
-        if R.ndim != 2 or wav.ndim != 1 or R.shape[1] != len(wav):
-            raise ValueError("spectrum_recover: R must be [n_orb][n_wav]")
+        wav, R = _spectrum(wav, R, "spectrum_recover")
         out, ptr = self._recover_outputs(n_comp, ones, orders, moments, records, totals, model)
         self._check(self.lib.prom_spectrum_recover(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(trial),
                                                    float(scale), int(bool(highpass)), int(n_comp), int(n_iter),

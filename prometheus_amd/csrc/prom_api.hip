@@ -10,48 +10,10 @@
 #include <mutex>
 #include <thread>
 
-#include "prom_internal.h"
+#include "prom_api_shared.h"
 #include "tw_stage.h"
-#include "vmap_index.h"
-#include "detrend_index.h"
-#include "highpass_index.h"
-#include "order_index.h"
-#include "broaden_index.h"
-#include "sysrem_index.h"
-#include "filter_index.h"
-
-using prom::DevBuf;
-using prom::Error;
 
 namespace {
-
-template <class F>
-int32_t guarded(prom_ctx* ctx, F&& f) {
-  if (!ctx) return PROM_E_ARG;
-  try {
-    PROM_HIP(hipSetDevice(ctx->device));
-    f();
-    ctx->err.clear();
-    return PROM_OK;
-  } catch (const Error& e) {
-    ctx->err = e.what();
-    return e.code;
-  } catch (const std::exception& e) {
-    ctx->err = e.what();
-    return PROM_E_HIP;
-  }
-}
-
-template <class T>
-void upload(DevBuf& b, const T* h, int64_t n, hipStream_t s) {
-  b.ensure(sizeof(T) * (size_t)std::max<int64_t>(n, 1));
-  if (n > 0) PROM_HIP(hipMemcpyAsync(b.p, h, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, s));
-}
-
-template <class T>
-void download(T* h, const DevBuf& b, int64_t n, hipStream_t s) {
-  if (n > 0) PROM_HIP(hipMemcpyAsync(h, b.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, s));
-}
 
 prom::DensityDev to_dev(const prom_density_model& m) {
   prom::DensityDev d{};
@@ -1820,1530 +1782,6 @@ int32_t prom_timing_end(prom_ctx* ctx, int32_t max_runs, double* ms, int32_t* n_
     }
     *n_runs = ctx->timed_runs;
     ctx->timed_runs = 0;
-  });
-}
-
-// ------------------------------------------------------------------------------ observation
-static bool obs_finite(double v) { return std::isfinite(v); }
-
-// the spectrum the transit observe calls read: the last run's R, or its broadened R_b while that is current
-// (prom_transit_broaden)
-static const double* transit_R(prom_ctx* ctx) {
-  const prom::TransitDev& tr = ctx->tr;
-  return ctx->br.current ? ctx->br.Rb.as<double>() : tr.slot[tr.last].R.as<double>();
-}
-
-int32_t prom_observe_set(prom_ctx* ctx, int32_t n_pix, const double* lam, const double* sig, double k, int32_t n_orb,
-                         const double* f, const double* data, const double* ivar) {
-  return guarded(ctx, [&] {
-    prom::ObsDev& ob = ctx->obs;
-    ob.set = false;
-    ctx->vm.set = false;   // a trial table belongs to the observation it was set for
-    ctx->vm.last_wav = ctx->vm.last_R = nullptr;
-    ctx->ex.set = false;   // ... and so does an exposure table (its data are in the observation's pixels)
-    ctx->ex.last_wav = ctx->ex.last_R = nullptr;
-    PROM_REQUIRE(n_pix >= 0 && n_orb >= 1 && n_orb <= 65535 && (n_pix == 0 || (lam && sig)),
-                 "prom_observe_set: bad shape");
-    PROM_REQUIRE(k > 0.0 && obs_finite(k), "prom_observe_set: the truncation k must be positive");
-    PROM_REQUIRE((data == nullptr) == (ivar == nullptr), "prom_observe_set: data and ivar come together");
-    for (int32_t p = 0; p < n_pix; ++p) {
-      PROM_REQUIRE(obs_finite(lam[p]) && (p == 0 || lam[p] >= lam[p - 1]),
-                   "prom_observe_set: pixel centres must be finite and non-decreasing");
-      PROM_REQUIRE(sig[p] > 0.0 && obs_finite(sig[p]), "prom_observe_set: widths must be positive");
-    }
-    bool ones = true;
-    for (int32_t o = 0; f && o < n_orb; ++o) {
-      PROM_REQUIRE(f[o] > 0.0 && obs_finite(f[o]), "prom_observe_set: frame factors must be positive");
-      ones = ones && f[o] == 1.0;
-    }
-    const hipStream_t st = ctx->stream;
-    const int64_t n = (int64_t)n_orb * n_pix;
-    upload(ob.lam, lam, n_pix, st);
-    upload(ob.sig, sig, n_pix, st);
-    ob.has_f = f && !ones;   // all ones: the shared-frame path, the same sums bit for bit
-    if (ob.has_f) upload(ob.f, f, n_orb, st);
-    ob.has_data = data != nullptr;
-    if (ob.has_data) {
-      upload(ob.data, data, n, st);
-      upload(ob.ivar, ivar, n, st);
-    }
-    ob.num.ensure(sizeof(double) * (size_t)std::max<int64_t>(n, 1));
-    ob.den.ensure(sizeof(double) * (size_t)std::max<int64_t>(n, 1));
-    ob.chi2.ensure(sizeof(double) * n_orb);
-    ob.n_used.ensure(sizeof(int64_t) * n_orb);
-    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
-    ob.n_pix = n_pix;
-    ob.n_orb = n_orb;
-    ob.k = k;
-    ob.last_wav = ob.last_R = nullptr;
-    ob.set = true;
-  });
-}
-
-// the shared tail of the two observe calls: q, the sums, chi-square and the copies back, on stream st
-static void observe_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav,
-                       double edge_lo, double edge_hi, double* num_out, double* den_out, double* chi2_out,
-                       int64_t* n_used_out) {
-  prom::ObsDev& ob = ctx->obs;
-  const bool want_chi2 = chi2_out || n_used_out;
-  const int64_t n = (int64_t)ob.n_orb * ob.n_pix;
-  ob.q.ensure(sizeof(double) * (size_t)n_wav);
-  prom::launch_observe_q(st, wav, (int32_t)n_wav, edge_lo, edge_hi, ob.q.as<double>());
-  prom::launch_observe(st, wav, ob.q.as<double>(), R, (int32_t)n_wav, ob.lam.as<double>(), ob.sig.as<double>(),
-                       ob.has_f ? ob.f.as<double>() : nullptr, ob.k, ob.n_pix, ob.n_orb, ob.num.as<double>(),
-                       ob.den.as<double>(), nullptr, nullptr);
-  ob.last_wav = wav;
-  ob.last_R = R;
-  ob.last_n_wav = (int32_t)n_wav;
-  if (want_chi2)
-    prom::launch_observe_chi2(st, ob.num.as<double>(), ob.den.as<double>(), ob.data.as<double>(),
-                              ob.ivar.as<double>(), ob.n_pix, ob.n_orb, ob.chi2.as<double>(),
-                              ob.n_used.as<int64_t>());
-  if (num_out) download(num_out, ob.num, n, st);
-  if (den_out) download(den_out, ob.den, n, st);
-  if (chi2_out) download(chi2_out, ob.chi2, ob.n_orb, st);
-  if (n_used_out) download(n_used_out, ob.n_used, ob.n_orb, st);
-  PROM_HIP(hipStreamSynchronize(st));
-}
-
-static void observe_check(const prom::ObsDev& ob, const char* who, double edge_lo, double edge_hi, bool want_chi2) {
-  if (!ob.set)
-    throw Error(PROM_E_STATE, std::string(who) + ": no observation on the context (prom_observe_set; a "
-                                                 "prom_transit_set with another n_orb drops it)");
-  PROM_REQUIRE(!want_chi2 || (edge_lo != edge_lo && edge_hi != edge_hi),
-               std::string(who) + ": chi-square needs the whole grid (both edges NaN)");
-  PROM_REQUIRE(!want_chi2 || ob.has_data, std::string(who) + ": chi-square needs data and ivar (prom_observe_set)");
-  PROM_REQUIRE(!std::isinf(edge_lo) && !std::isinf(edge_hi), std::string(who) + ": infinite edge");
-}
-
-int32_t prom_transit_observe(prom_ctx* ctx, double edge_lo, double edge_hi, double* num_out, double* den_out,
-                             double* chi2_out, int64_t* n_used_out) {
-  return guarded(ctx, [&] {
-    prom::TransitDev& tr = ctx->tr;
-    prom::ObsDev& ob = ctx->obs;
-    observe_check(ob, "prom_transit_observe", edge_lo, edge_hi, chi2_out || n_used_out);
-    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_observe: no completed run");
-    if (ob.n_orb != tr.n_orb) throw Error(PROM_E_STATE, "prom_transit_observe: the observation has another n_orb");
-    PROM_REQUIRE(!ctx->br.current || (edge_lo != edge_lo && edge_hi != edge_hi),
-                 "prom_transit_observe: the broadened spectrum covers the whole grid (both edges NaN)");
-    if (ob.n_pix == 0) return;
-    // the last run's stream orders the observation after it
-    observe_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, edge_lo,
-               edge_hi, num_out, den_out, chi2_out, n_used_out);
-  });
-}
-
-int32_t prom_spectrum_observe(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
-                              double edge_lo, double edge_hi, double* num_out, double* den_out, double* chi2_out,
-                              int64_t* n_used_out) {
-  return guarded(ctx, [&] {
-    prom::ObsDev& ob = ctx->obs;
-    observe_check(ob, "prom_spectrum_observe", edge_lo, edge_hi, chi2_out || n_used_out);
-    PROM_REQUIRE(n_orb == ob.n_orb, "prom_spectrum_observe: n_orb differs from the observation's");
-    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_observe: bad spectrum");
-    for (int64_t w = 0; w < n_wav; ++w)
-      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
-                   "prom_spectrum_observe: wavelengths must be finite and ascending");
-    PROM_REQUIRE((edge_lo != edge_lo || edge_lo <= wav[0]) && (edge_hi != edge_hi || edge_hi >= wav[n_wav - 1]),
-                 "prom_spectrum_observe: the edges lie outside the grid");
-    if (ob.n_pix == 0) return;
-    const hipStream_t st = ctx->stream;
-    upload(ob.wav, wav, n_wav, st);
-    upload(ob.R, R, (int64_t)n_orb * n_wav, st);
-    observe_on(ctx, st, ob.wav.as<double>(), ob.R.as<double>(), n_wav, edge_lo, edge_hi, num_out, den_out, chi2_out,
-               n_used_out);
-  });
-}
-
-int32_t prom_observe_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
-  return guarded(ctx, [&] {
-    prom::ObsDev& ob = ctx->obs;
-    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_observe_kernel_ms: bad arguments");
-    if (!ob.set || !ob.last_wav || ob.n_pix == 0)
-      throw Error(PROM_E_STATE, "prom_observe_kernel_ms: no observe call to repeat");
-    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
-    const hipStream_t st = ctx->stream;
-    double sum = 0.0;
-    for (int32_t r = 0; r < n_runs; ++r) {
-      prom::launch_observe(st, ob.last_wav, ob.q.as<double>(), ob.last_R, ob.last_n_wav, ob.lam.as<double>(),
-                           ob.sig.as<double>(), ob.has_f ? ob.f.as<double>() : nullptr, ob.k, ob.n_pix, ob.n_orb,
-                           ob.num.as<double>(), ob.den.as<double>(), ctx->ev[0], ctx->ev[1]);
-      PROM_HIP(hipStreamSynchronize(st));
-      float ms = 0.0f;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      sum += ms;
-    }
-    *ms_out = sum / n_runs;
-  });
-}
-
-// ------------------------------------------------------------------------------ velocity maps
-int32_t prom_vmap_set(prom_ctx* ctx, int32_t n_orb, int32_t n_trial, const double* F) {
-  return guarded(ctx, [&] {
-    prom::VmDev& vm = ctx->vm;
-    const prom::ObsDev& ob = ctx->obs;
-    vm.set = false;
-    vm.last_wav = vm.last_R = nullptr;
-    PROM_REQUIRE(n_orb >= 1 && n_trial >= 1 && n_trial <= (1 << 24) && F, "prom_vmap_set: bad shape");
-    if (!ob.set)
-      throw Error(PROM_E_STATE, "prom_vmap_set: no observation on the context (prom_observe_set)");
-    if (!ob.has_data)
-      throw Error(PROM_E_STATE, "prom_vmap_set: the observation has no data and ivar (prom_observe_set)");
-    if (ob.n_orb != n_orb) throw Error(PROM_E_STATE, "prom_vmap_set: the observation has another n_orb");
-    const int64_t n = (int64_t)n_orb * n_trial;
-    PROM_REQUIRE(n <= ((int64_t)1 << 28), "prom_vmap_set: table too large");
-    for (int64_t i = 0; i < n; ++i)
-      PROM_REQUIRE(F[i] > 0.0 && obs_finite(F[i]), "prom_vmap_set: trial factors must be finite and positive");
-    const hipStream_t st = ctx->stream;
-    upload(vm.F, F, n, st);
-    vm.mom.ensure(sizeof(double) * 7 * (size_t)n);
-    vm.n_used.ensure(sizeof(int64_t) * (size_t)n);
-    PROM_HIP(hipStreamSynchronize(st));   // the host array is read during the call only
-    vm.n_orb = n_orb;
-    vm.n_trial = n_trial;
-    vm.set = true;
-  });
-}
-
-// one pass over the table in batches of whole trial groups (ev: events around the k_vmap launches of the first batch)
-static void vmap_launch(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int32_t n_wav,
-                        hipEvent_t ev0, hipEvent_t ev1) {
-  prom::VmDev& vm = ctx->vm;
-  const prom::ObsDev& ob = ctx->obs;
-  const int32_t n_chunks = prom::vm_chunks(ob.n_pix), n_groups = prom::vm_groups(vm.n_trial);
-  const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, vm.n_orb, n_chunks, n_groups);
-  const int32_t nb_max = std::min(bg * prom::kVmTrials, vm.n_trial);
-  vm.part.ensure(sizeof(double) * (size_t)prom::vm_part_doubles(vm.n_orb, nb_max, n_chunks));
-  static const bool debug = std::getenv("PROM_DEBUG") != nullptr;
-  if (debug)
-    std::fprintf(stderr, "prom: velocity map: %d trials in %d groups, %d batches of up to %d groups, %d chunks\n",
-                 vm.n_trial, n_groups, (n_groups + bg - 1) / bg, bg, n_chunks);
-  for (int32_t g = 0; g < n_groups; g += bg) {
-    const int32_t j_first = prom::vm_group_first(g), nb = std::min(nb_max, vm.n_trial - j_first);
-    prom::launch_vmap(st, wav, vm.q.as<double>(), R, n_wav, ob.lam.as<double>(), ob.sig.as<double>(), ob.k,
-                      ob.data.as<double>(), ob.ivar.as<double>(), vm.F.as<double>(), ob.n_pix, vm.n_orb, vm.n_trial,
-                      j_first, nb, vm.part.as<double>(), g == 0 ? ev0 : nullptr, g == 0 ? ev1 : nullptr);
-    prom::launch_vmap_reduce(st, vm.part.as<double>(), ob.n_pix, vm.n_orb, vm.n_trial, j_first, nb,
-                             vm.mom.as<double>(), vm.n_used.as<int64_t>());
-  }
-}
-
-// the shared tail of the two map calls: q of the whole grid, the batches and the copies back, on stream st
-static void vmap_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, double* mom_out,
-                    int64_t* n_used_out) {
-  prom::VmDev& vm = ctx->vm;
-  const int64_t n = (int64_t)vm.n_orb * vm.n_trial;
-  if (ctx->obs.n_pix == 0) {   // no pixel is used: every moment 0
-    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
-    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
-    return;
-  }
-  const double nan = std::nan("");
-  vm.q.ensure(sizeof(double) * (size_t)n_wav);
-  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, vm.q.as<double>());
-  vmap_launch(ctx, st, wav, R, (int32_t)n_wav, nullptr, nullptr);
-  vm.last_wav = wav;
-  vm.last_R = R;
-  vm.last_n_wav = (int32_t)n_wav;
-  if (mom_out) download(mom_out, vm.mom, 7 * n, st);
-  if (n_used_out) download(n_used_out, vm.n_used, n, st);
-  PROM_HIP(hipStreamSynchronize(st));
-}
-
-static void vmap_check(prom_ctx* ctx, const char* who) {
-  if (!ctx->vm.set || !ctx->obs.set || !ctx->obs.has_data || ctx->obs.n_orb != ctx->vm.n_orb)
-    throw Error(PROM_E_STATE, std::string(who) + ": no trial table on the context (prom_vmap_set; a later "
-                                                 "prom_observe_set or a prom_transit_set with another n_orb drops it)");
-}
-
-int32_t prom_transit_vmap(prom_ctx* ctx, double* mom_out, int64_t* n_used_out) {
-  return guarded(ctx, [&] {
-    prom::TransitDev& tr = ctx->tr;
-    vmap_check(ctx, "prom_transit_vmap");
-    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_vmap: no completed run");
-    if (ctx->vm.n_orb != tr.n_orb) throw Error(PROM_E_STATE, "prom_transit_vmap: the trial table has another n_orb");
-    // the last run's stream orders the map after it
-    vmap_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, mom_out,
-            n_used_out);
-  });
-}
-
-int32_t prom_spectrum_vmap(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
-                           double* mom_out, int64_t* n_used_out) {
-  return guarded(ctx, [&] {
-    prom::VmDev& vm = ctx->vm;
-    vmap_check(ctx, "prom_spectrum_vmap");
-    PROM_REQUIRE(n_orb == vm.n_orb, "prom_spectrum_vmap: n_orb differs from the trial table's");
-    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_vmap: bad spectrum");
-    for (int64_t w = 0; w < n_wav; ++w)
-      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
-                   "prom_spectrum_vmap: wavelengths must be finite and ascending");
-    const hipStream_t st = ctx->stream;
-    vm.last_wav = vm.last_R = nullptr;   // (the uploads may move the buffers the last map read)
-    upload(vm.wav, wav, n_wav, st);
-    upload(vm.R, R, (int64_t)n_orb * n_wav, st);
-    vmap_on(ctx, st, vm.wav.as<double>(), vm.R.as<double>(), n_wav, mom_out, n_used_out);
-  });
-}
-
-int32_t prom_vmap_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
-  return guarded(ctx, [&] {
-    prom::VmDev& vm = ctx->vm;
-    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_vmap_kernel_ms: bad arguments");
-    if (!vm.set || !ctx->obs.set || !vm.last_wav || ctx->obs.n_pix == 0)
-      throw Error(PROM_E_STATE, "prom_vmap_kernel_ms: no map call to repeat");
-    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
-    const hipStream_t st = ctx->stream;
-    // k_vmap of the first batch (the whole table when it fits the scratch cap), scaled to the table by trial count
-    const int32_t n_groups = prom::vm_groups(vm.n_trial);
-    const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, vm.n_orb, prom::vm_chunks(ctx->obs.n_pix), n_groups);
-    const double scale = (double)vm.n_trial / (double)std::min(bg * prom::kVmTrials, vm.n_trial);
-    double sum = 0.0;
-    for (int32_t r = 0; r < n_runs; ++r) {
-      vmap_launch(ctx, st, vm.last_wav, vm.last_R, vm.last_n_wav, ctx->ev[0], ctx->ev[1]);
-      PROM_HIP(hipStreamSynchronize(st));
-      float ms = 0.0f;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      sum += ms;
-    }
-    *ms_out = scale * sum / n_runs;
-  });
-}
-
-// ------------------------------------------------------------------------------ exposures
-int32_t prom_expose_set(prom_ctx* ctx, int32_t n_exp, int32_t n_trial, int32_t n_tap, const int32_t* row,
-                        const double* a, const double* F, const double* data, const double* ivar) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    const prom::ObsDev& ob = ctx->obs;
-    ex.set = false;
-    ex.dt_set = ex.dt_ran = false;   // a filter belongs to the table it was set for
-    ex.hp_set = ex.hp_ran = false;   // ... and so does a high-pass
-    ex.od_set = ex.od_ran = false;   // ... and the orders of the per-order moments
-    ctx->sy.set = false;             // ... and the raw exposures of the injections
-    ctx->sy.last_source = 0;
-    ctx->rc.last = 0;
-    ex.last_wav = ex.last_R = nullptr;
-    PROM_REQUIRE(n_exp >= 1 && n_exp <= 65535 && n_trial >= 1 && n_trial <= (1 << 24) && n_tap >= 1 &&
-                     n_tap <= (1 << 16) && row && a && F,
-                 "prom_expose_set: bad shape");
-    if (!ob.set) throw Error(PROM_E_STATE, "prom_expose_set: no observation on the context (prom_observe_set)");
-    PROM_REQUIRE(ob.n_pix == 0 || (data && ivar), "prom_expose_set: data and ivar missing");
-    const int64_t nt = (int64_t)n_exp * n_tap, nf = nt * n_trial, nd = (int64_t)n_exp * ob.n_pix;
-    PROM_REQUIRE(nf <= ((int64_t)1 << 28), "prom_expose_set: table too large");
-    for (int64_t i = 0; i < nt; ++i) {
-      PROM_REQUIRE(row[i] >= 0 && row[i] < ob.n_orb, "prom_expose_set: a tap's row lies outside [0, n_orb)");
-      PROM_REQUIRE(a[i] >= 0.0 && obs_finite(a[i]), "prom_expose_set: tap weights must be finite and >= 0");
-    }
-    for (int64_t i = 0; i < nf; ++i)
-      PROM_REQUIRE(F[i] > 0.0 && obs_finite(F[i]), "prom_expose_set: factors must be finite and positive");
-    const hipStream_t st = ctx->stream;
-    upload(ex.row, row, nt, st);
-    upload(ex.a, a, nt, st);
-    upload(ex.F, F, nf, st);
-    upload(ex.data, data, nd, st);
-    upload(ex.ivar, ivar, nd, st);
-    ex.mom.ensure(sizeof(double) * 7 * (size_t)n_exp * n_trial);
-    ex.n_used.ensure(sizeof(int64_t) * (size_t)n_exp * n_trial);
-    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
-    ex.n_orb = ob.n_orb;
-    ex.n_exp = n_exp;
-    ex.n_trial = n_trial;
-    ex.n_tap = n_tap;
-    ex.set = true;
-  });
-}
-
-// one pass over the table in batches of whole trial groups (ev: events around the k_expose launch of the first batch)
-static void expose_launch(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int32_t n_wav,
-                          bool want_mom, double* model, hipEvent_t ev0, hipEvent_t ev1) {
-  prom::ExDev& ex = ctx->ex;
-  const prom::ObsDev& ob = ctx->obs;
-  const int32_t n_chunks = prom::vm_chunks(ob.n_pix), n_groups = prom::vm_groups(ex.n_trial);
-  const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, n_chunks, n_groups);
-  const int32_t nb_max = std::min(bg * prom::kVmTrials, ex.n_trial);
-  ex.part.ensure(sizeof(double) * (size_t)prom::vm_part_doubles(ex.n_exp, nb_max, n_chunks));
-  static const bool debug = std::getenv("PROM_DEBUG") != nullptr;
-  if (debug)
-    std::fprintf(stderr, "prom: exposures: %d trials in %d groups, %d batches of up to %d groups, %d chunks\n",
-                 ex.n_trial, n_groups, (n_groups + bg - 1) / bg, bg, n_chunks);
-  for (int32_t g = 0; g < n_groups; g += bg) {
-    const int32_t j_first = prom::vm_group_first(g), nb = std::min(nb_max, ex.n_trial - j_first);
-    prom::launch_expose(st, wav, ex.q.as<double>(), R, n_wav, ob.lam.as<double>(), ob.sig.as<double>(), ob.k,
-                        ex.row.as<int32_t>(), ex.a.as<double>(), ex.F.as<double>(), ex.data.as<double>(),
-                        ex.ivar.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, ex.n_tap, j_first, nb,
-                        ex.part.as<double>(), model, g == 0 ? ev0 : nullptr, g == 0 ? ev1 : nullptr);
-    if (want_mom)
-      prom::launch_vmap_reduce(st, ex.part.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, j_first, nb,
-                               ex.mom.as<double>(), ex.n_used.as<int64_t>());
-  }
-}
-
-// the shared tail of the two expose calls: q of the whole grid, the batches and the copies back, on stream st
-static void expose_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, double* mom_out,
-                      int64_t* n_used_out, double* model_out) {
-  prom::ExDev& ex = ctx->ex;
-  const int64_t n = (int64_t)ex.n_exp * ex.n_trial;
-  if (ctx->obs.n_pix == 0) {   // no pixel: every moment 0 and no model value
-    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
-    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
-    return;
-  }
-  if (!mom_out && !n_used_out && !model_out) return;
-  const double nan = std::nan("");
-  const int64_t nm = n * ctx->obs.n_pix;
-  ex.q.ensure(sizeof(double) * (size_t)n_wav);
-  if (model_out) ex.model.ensure(sizeof(double) * (size_t)nm);
-  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
-  expose_launch(ctx, st, wav, R, (int32_t)n_wav, mom_out || n_used_out, model_out ? ex.model.as<double>() : nullptr,
-                nullptr, nullptr);
-  ex.last_wav = wav;
-  ex.last_R = R;
-  ex.last_n_wav = (int32_t)n_wav;
-  ex.dt_ran = ex.hp_ran = ex.od_ran = false;
-  if (mom_out) download(mom_out, ex.mom, 7 * n, st);
-  if (n_used_out) download(n_used_out, ex.n_used, n, st);
-  if (model_out) download(model_out, ex.model, nm, st);
-  PROM_HIP(hipStreamSynchronize(st));
-}
-
-static void expose_check(prom_ctx* ctx, const char* who) {
-  if (!ctx->ex.set || !ctx->obs.set || ctx->obs.n_orb != ctx->ex.n_orb)
-    throw Error(PROM_E_STATE, std::string(who) + ": no exposure table on the context (prom_expose_set; a later "
-                                                 "prom_observe_set or a prom_transit_set with another n_orb drops it)");
-}
-
-int32_t prom_transit_expose(prom_ctx* ctx, double* mom_out, int64_t* n_used_out, double* model_out) {
-  return guarded(ctx, [&] {
-    prom::TransitDev& tr = ctx->tr;
-    expose_check(ctx, "prom_transit_expose");
-    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose: no completed run");
-    if (ctx->ex.n_orb != tr.n_orb)
-      throw Error(PROM_E_STATE, "prom_transit_expose: the exposure table has another n_orb");
-    // the last run's stream orders the exposures after it
-    expose_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, mom_out,
-              n_used_out, model_out);
-  });
-}
-
-int32_t prom_spectrum_expose(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
-                             double* mom_out, int64_t* n_used_out, double* model_out) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    expose_check(ctx, "prom_spectrum_expose");
-    PROM_REQUIRE(n_orb == ex.n_orb, "prom_spectrum_expose: n_orb differs from the observation's");
-    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_expose: bad spectrum");
-    for (int64_t w = 0; w < n_wav; ++w)
-      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
-                   "prom_spectrum_expose: wavelengths must be finite and ascending");
-    const hipStream_t st = ctx->stream;
-    ex.last_wav = ex.last_R = nullptr;   // (the uploads may move the buffers the last call read)
-    upload(ex.wav, wav, n_wav, st);
-    upload(ex.R, R, (int64_t)n_orb * n_wav, st);
-    expose_on(ctx, st, ex.wav.as<double>(), ex.R.as<double>(), n_wav, mom_out, n_used_out, model_out);
-  });
-}
-
-int32_t prom_expose_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_expose_kernel_ms: bad arguments");
-    if (!ex.set || !ctx->obs.set || !ex.last_wav || ctx->obs.n_pix == 0)
-      throw Error(PROM_E_STATE, "prom_expose_kernel_ms: no expose call to repeat");
-    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
-    const hipStream_t st = ctx->stream;
-    // k_expose of the first batch (the whole table when it fits the scratch cap), scaled to the table by trial count;
-    // moments only, no model store
-    const int32_t n_groups = prom::vm_groups(ex.n_trial);
-    const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, prom::vm_chunks(ctx->obs.n_pix), n_groups);
-    const double scale = (double)ex.n_trial / (double)std::min(bg * prom::kVmTrials, ex.n_trial);
-    double sum = 0.0;
-    for (int32_t r = 0; r < n_runs; ++r) {
-      expose_launch(ctx, st, ex.last_wav, ex.last_R, ex.last_n_wav, true, nullptr, ctx->ev[0], ctx->ev[1]);
-      PROM_HIP(hipStreamSynchronize(st));
-      float ms = 0.0f;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      sum += ms;
-    }
-    *ms_out = scale * sum / n_runs;
-  });
-}
-
-// ------------------------------------------------------------------------------ detrended exposures
-int32_t prom_detrend_set(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, const double* U, const double* W) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    ex.dt_set = ex.dt_ran = false;
-    if (ctx->rc.last == 1) ctx->rc.last = 0;
-    if (!ex.set || !ctx->obs.set || ctx->obs.n_orb != ex.n_orb)
-      throw Error(PROM_E_STATE, "prom_detrend_set: no exposure table on the context (prom_expose_set)");
-    PROM_REQUIRE(n_exp == ex.n_exp, "prom_detrend_set: n_exp differs from the exposure table's");
-    PROM_REQUIRE(n_comp >= 1 && n_comp <= prom::kDtMaxComp, "prom_detrend_set: n_comp must lie in [1, 16]");
-    const int64_t nu = (int64_t)n_exp * n_comp, nw = nu * ctx->obs.n_pix;
-    PROM_REQUIRE(U && (nw == 0 || W), "prom_detrend_set: U and W missing");
-    for (int64_t i = 0; i < nu; ++i) PROM_REQUIRE(obs_finite(U[i]), "prom_detrend_set: U must be finite");
-    for (int64_t i = 0; i < nw; ++i) PROM_REQUIRE(obs_finite(W[i]), "prom_detrend_set: W must be finite");
-    const hipStream_t st = ctx->stream;
-    upload(ex.U, U, nu, st);
-    upload(ex.W, W, nw, st);
-    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
-    ex.n_comp = n_comp;
-    ex.dt_set = true;
-  });
-}
-
-// the moments of the model in ex.model, in batches of whole trial groups (ev: events around the first batch's
-// k_model_moments; data: what stands in the place of the table's data, the recovery's cleaned exposures)
-static void moments_launch(prom_ctx* ctx, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
-                           const double* data = nullptr) {
-  prom::ExDev& ex = ctx->ex;
-  const prom::ObsDev& ob = ctx->obs;
-  const int32_t n_chunks = prom::vm_chunks(ob.n_pix), n_groups = prom::vm_groups(ex.n_trial);
-  const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, n_chunks, n_groups);
-  const int32_t nb_max = std::min(bg * prom::kVmTrials, ex.n_trial);
-  ex.part.ensure(sizeof(double) * (size_t)prom::vm_part_doubles(ex.n_exp, nb_max, n_chunks));
-  static const bool debug = std::getenv("PROM_DEBUG") != nullptr;
-  if (debug)
-    std::fprintf(stderr, "prom: detrended moments: %d trials in %d groups, %d batches of up to %d groups, %d chunks\n",
-                 ex.n_trial, n_groups, (n_groups + bg - 1) / bg, bg, n_chunks);
-  for (int32_t g = 0; g < n_groups; g += bg) {
-    const int32_t j_first = prom::vm_group_first(g), nb = std::min(nb_max, ex.n_trial - j_first);
-    prom::launch_model_moments(st, ex.model.as<double>(), ex.flag.as<uint8_t>(), data ? data : ex.data.as<double>(),
-                               ex.ivar.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, j_first, nb, ex.part.as<double>(),
-                               g == 0 ? ev0 : nullptr, g == 0 ? ev1 : nullptr);
-    prom::launch_vmap_reduce(st, ex.part.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, j_first, nb, ex.mom.as<double>(),
-                             ex.n_used.as<int64_t>());
-  }
-}
-
-// the unfiltered model of the whole table into ex.model (k_expose without moments), then the filter in place
-static void detrend_model(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int32_t n_wav,
-                          hipEvent_t ev0, hipEvent_t ev1) {
-  prom::ExDev& ex = ctx->ex;
-  expose_launch(ctx, st, wav, R, n_wav, false, ex.model.as<double>(), nullptr, nullptr);
-  prom::launch_detrend(st, ex.model.as<double>(), ex.U.as<double>(), ex.W.as<double>(), ex.flag.as<uint8_t>(),
-                       ex.n_exp, ex.n_comp, ex.n_trial, ctx->obs.n_pix, ev0, ev1);
-}
-
-// the shared tail of the two detrended calls, on stream st
-static void detrend_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav,
-                       double* mom_out, int64_t* n_used_out, double* model_out) {
-  prom::ExDev& ex = ctx->ex;
-  const int64_t n = (int64_t)ex.n_exp * ex.n_trial;
-  if (ctx->obs.n_pix == 0) {   // no pixel: every moment 0 and no model value
-    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
-    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
-    return;
-  }
-  if (!mom_out && !n_used_out && !model_out) return;
-  const double nan = std::nan("");
-  const int64_t nm = n * ctx->obs.n_pix;
-  ex.q.ensure(sizeof(double) * (size_t)n_wav);
-  try {   // the whole table's model is resident at once: it is not batched
-    ex.model.ensure(sizeof(double) * (size_t)nm);
-  } catch (const Error& err) {
-    throw Error(err.code, std::string(err.what()) + ": the detrended exposures keep the model of all " +
-                              std::to_string(ex.n_trial) + " trials in device memory; give fewer trials per call");
-  }
-  ex.flag.ensure((size_t)ex.n_trial * ctx->obs.n_pix);
-  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
-  detrend_model(ctx, st, wav, R, (int32_t)n_wav, nullptr, nullptr);
-  if (mom_out || n_used_out) moments_launch(ctx, st, nullptr, nullptr);
-  ex.last_wav = wav;
-  ex.last_R = R;
-  ex.last_n_wav = (int32_t)n_wav;
-  ex.dt_ran = true;
-  ex.hp_ran = ex.od_ran = false;
-  if (mom_out) download(mom_out, ex.mom, 7 * n, st);
-  if (n_used_out) download(n_used_out, ex.n_used, n, st);
-  if (model_out) download(model_out, ex.model, nm, st);
-  PROM_HIP(hipStreamSynchronize(st));
-}
-
-static void detrend_check(prom_ctx* ctx, const char* who) {
-  expose_check(ctx, who);
-  if (!ctx->ex.dt_set)
-    throw Error(PROM_E_STATE, std::string(who) + ": no filter on the context (prom_detrend_set; a later "
-                                                 "prom_expose_set, or whatever drops the exposure table, drops it)");
-}
-
-int32_t prom_transit_expose_detrended(prom_ctx* ctx, double* mom_out, int64_t* n_used_out, double* model_out) {
-  return guarded(ctx, [&] {
-    prom::TransitDev& tr = ctx->tr;
-    detrend_check(ctx, "prom_transit_expose_detrended");
-    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose_detrended: no completed run");
-    if (ctx->ex.n_orb != tr.n_orb)
-      throw Error(PROM_E_STATE, "prom_transit_expose_detrended: the exposure table has another n_orb");
-    detrend_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, mom_out,
-               n_used_out, model_out);
-  });
-}
-
-int32_t prom_spectrum_expose_detrended(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
-                                       double* mom_out, int64_t* n_used_out, double* model_out) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    detrend_check(ctx, "prom_spectrum_expose_detrended");
-    PROM_REQUIRE(n_orb == ex.n_orb, "prom_spectrum_expose_detrended: n_orb differs from the observation's");
-    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_expose_detrended: bad spectrum");
-    for (int64_t w = 0; w < n_wav; ++w)
-      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
-                   "prom_spectrum_expose_detrended: wavelengths must be finite and ascending");
-    const hipStream_t st = ctx->stream;
-    ex.last_wav = ex.last_R = nullptr;   // (the uploads may move the buffers the last call read)
-    upload(ex.wav, wav, n_wav, st);
-    upload(ex.R, R, (int64_t)n_orb * n_wav, st);
-    detrend_on(ctx, st, ex.wav.as<double>(), ex.R.as<double>(), n_wav, mom_out, n_used_out, model_out);
-  });
-}
-
-int32_t prom_detrend_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_detrend_kernel_ms: bad arguments");
-    if (!ex.set || !ex.dt_set || !ex.dt_ran || !ctx->obs.set || !ex.last_wav || ctx->obs.n_pix == 0)
-      throw Error(PROM_E_STATE, "prom_detrend_kernel_ms: no detrended call to repeat");
-    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
-    const hipStream_t st = ctx->stream;
-    // the filter works in place, so every repetition forms the unfiltered model again (untimed) before k_detrend
-    // (timed, the whole table); k_model_moments of the first batch, scaled to the table by trial count
-    const int32_t n_groups = prom::vm_groups(ex.n_trial);
-    const int32_t bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, prom::vm_chunks(ctx->obs.n_pix), n_groups);
-    const double scale = (double)ex.n_trial / (double)std::min(bg * prom::kVmTrials, ex.n_trial);
-    double sum[2] = {0.0, 0.0};
-    for (int32_t r = 0; r < n_runs; ++r) {
-      detrend_model(ctx, st, ex.last_wav, ex.last_R, ex.last_n_wav, ctx->ev[0], ctx->ev[1]);
-      moments_launch(ctx, st, ctx->ev[2], ctx->ev[3]);
-      PROM_HIP(hipStreamSynchronize(st));
-      float ms = 0.0f;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      sum[0] += ms;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-      sum[1] += ms;
-    }
-    ms_out[0] = sum[0] / n_runs;
-    ms_out[1] = scale * sum[1] / n_runs;
-  });
-}
-
-// ------------------------------------------------------------------------------ high-pass filtered exposures
-int32_t prom_highpass_set(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32_t* seg_first, const int32_t* perm,
-                          int32_t half_width, const double* g, int32_t mode) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    ex.hp_set = ex.hp_ran = false;
-    if (!ex.set || !ctx->obs.set || ctx->obs.n_orb != ex.n_orb)
-      throw Error(PROM_E_STATE, "prom_highpass_set: no exposure table on the context (prom_expose_set)");
-    PROM_REQUIRE(n_pix == ctx->obs.n_pix, "prom_highpass_set: n_pix differs from the observation's");
-    PROM_REQUIRE(n_seg >= 1 && seg_first && (n_pix == 0 || perm), "prom_highpass_set: segments missing");
-    PROM_REQUIRE(half_width >= 0 && half_width <= prom::kHpMaxHalf && g,
-                 "prom_highpass_set: half_width must lie in [0, 512]");
-    PROM_REQUIRE(mode == 0 || mode == 1, "prom_highpass_set: mode must be 0 (subtract) or 1 (divide)");
-    if (n_pix == 0) {   // no pixel: no segment can hold one; the calls give zeros
-      PROM_REQUIRE(n_seg == 1 && seg_first[0] == 0 && seg_first[1] == 0,
-                   "prom_highpass_set: without pixels seg_first must be {0, 0}");
-    } else {
-      PROM_REQUIRE(n_seg <= n_pix && seg_first[0] == 0 && seg_first[n_seg] == n_pix,
-                   "prom_highpass_set: seg_first must run from 0 to n_pix");
-      for (int32_t i = 0; i < n_seg; ++i)
-        PROM_REQUIRE(seg_first[i + 1] > seg_first[i], "prom_highpass_set: seg_first must be strictly ascending");
-      std::vector<char> seen((size_t)n_pix, 0);
-      for (int32_t i = 0; i < n_pix; ++i) {
-        PROM_REQUIRE(perm[i] >= 0 && perm[i] < n_pix && !seen[(size_t)perm[i]],
-                     "prom_highpass_set: perm must be a permutation of 0 .. n_pix - 1");
-        seen[(size_t)perm[i]] = 1;
-      }
-    }
-    for (int32_t d = 0; d <= half_width; ++d)
-      PROM_REQUIRE(obs_finite(g[d]) && g[d] >= 0.0, "prom_highpass_set: g must be finite and >= 0");
-    PROM_REQUIRE(g[0] > 0.0, "prom_highpass_set: g[0] must be > 0");
-    const hipStream_t st = ctx->stream;
-    upload(ex.hp_seg, seg_first, (int64_t)n_seg + 1, st);
-    upload(ex.hp_perm, perm, (int64_t)n_pix, st);
-    upload(ex.hp_g, g, (int64_t)half_width + 1, st);
-    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
-    ex.hp_n_seg = n_seg;
-    ex.hp_half = half_width;
-    ex.hp_mode = mode;
-    ex.hp_den = prom::hp_den_full(g, half_width);
-    ex.hp_set = true;
-  });
-}
-
-// the unfiltered model of the whole table into ex.model (k_expose without moments), the high-pass in place (ev:
-// events around k_highpass), then the SYSREM filter in place or every column flagged filterable
-static void highpass_model(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int32_t n_wav,
-                           int32_t detrend, hipEvent_t ev0, hipEvent_t ev1) {
-  prom::ExDev& ex = ctx->ex;
-  const int32_t n_pix = ctx->obs.n_pix;
-  expose_launch(ctx, st, wav, R, n_wav, false, ex.model.as<double>(), nullptr, nullptr);
-  prom::launch_highpass(st, ex.model.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(),
-                        ex.hp_g.as<double>(), ex.hp_half, ex.hp_den, ex.hp_mode, (int64_t)ex.n_exp * ex.n_trial,
-                        ex.hp_n_seg, n_pix, ev0, ev1);
-  if (detrend)
-    prom::launch_detrend(st, ex.model.as<double>(), ex.U.as<double>(), ex.W.as<double>(), ex.flag.as<uint8_t>(),
-                         ex.n_exp, ex.n_comp, ex.n_trial, n_pix, nullptr, nullptr);
-  else
-    PROM_HIP(hipMemsetAsync(ex.flag.as<uint8_t>(), 1, (size_t)ex.n_trial * n_pix, st));
-}
-
-// the shared tail of the two high-pass calls, on stream st
-static void highpass_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav,
-                        int32_t detrend, double* mom_out, int64_t* n_used_out, double* model_out) {
-  prom::ExDev& ex = ctx->ex;
-  const int64_t n = (int64_t)ex.n_exp * ex.n_trial;
-  if (ctx->obs.n_pix == 0) {   // no pixel: every moment 0 and no model value
-    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
-    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
-    return;
-  }
-  if (!mom_out && !n_used_out && !model_out) return;
-  if (prom::hp_workgroups(n, ex.hp_n_seg) > (((int64_t)1 << 31) - 1))   // (before anything is launched)
-    throw Error(PROM_E_ARG, "k_highpass: n_exp n_trial n_seg too large for one launch");
-  const double nan = std::nan("");
-  const int64_t nm = n * ctx->obs.n_pix;
-  ex.q.ensure(sizeof(double) * (size_t)n_wav);
-  try {   // the whole table's model is resident at once: it is not batched
-    ex.model.ensure(sizeof(double) * (size_t)nm);
-  } catch (const Error& err) {
-    throw Error(err.code, std::string(err.what()) + ": the high-pass filtered exposures keep the model of all " +
-                              std::to_string(ex.n_trial) + " trials in device memory; give fewer trials per call");
-  }
-  ex.flag.ensure((size_t)ex.n_trial * ctx->obs.n_pix);
-  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
-  highpass_model(ctx, st, wav, R, (int32_t)n_wav, detrend, nullptr, nullptr);
-  if (mom_out || n_used_out) moments_launch(ctx, st, nullptr, nullptr);
-  ex.last_wav = wav;
-  ex.last_R = R;
-  ex.last_n_wav = (int32_t)n_wav;
-  ex.dt_ran = ex.od_ran = false;
-  ex.hp_ran = true;
-  ex.hp_detrend = detrend;
-  if (mom_out) download(mom_out, ex.mom, 7 * n, st);
-  if (n_used_out) download(n_used_out, ex.n_used, n, st);
-  if (model_out) download(model_out, ex.model, nm, st);
-  PROM_HIP(hipStreamSynchronize(st));
-}
-
-static void highpass_check(prom_ctx* ctx, const char* who, int32_t detrend) {
-  expose_check(ctx, who);
-  if (!ctx->ex.hp_set)
-    throw Error(PROM_E_STATE, std::string(who) + ": no high-pass on the context (prom_highpass_set; a later "
-                                                 "prom_expose_set, or whatever drops the exposure table, drops it)");
-  if (detrend != 0 && detrend != 1) throw Error(PROM_E_ARG, std::string(who) + ": detrend must be 0 or 1");
-  if (detrend && !ctx->ex.dt_set)
-    throw Error(PROM_E_STATE, std::string(who) + ": detrend = 1 without a filter on the context (prom_detrend_set)");
-}
-
-int32_t prom_transit_expose_highpass(prom_ctx* ctx, int32_t detrend, double* mom_out, int64_t* n_used_out,
-                                     double* model_out) {
-  return guarded(ctx, [&] {
-    prom::TransitDev& tr = ctx->tr;
-    highpass_check(ctx, "prom_transit_expose_highpass", detrend);
-    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose_highpass: no completed run");
-    if (ctx->ex.n_orb != tr.n_orb)
-      throw Error(PROM_E_STATE, "prom_transit_expose_highpass: the exposure table has another n_orb");
-    highpass_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, detrend,
-                mom_out, n_used_out, model_out);
-  });
-}
-
-int32_t prom_spectrum_expose_highpass(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
-                                      int32_t detrend, double* mom_out, int64_t* n_used_out, double* model_out) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    highpass_check(ctx, "prom_spectrum_expose_highpass", detrend);
-    PROM_REQUIRE(n_orb == ex.n_orb, "prom_spectrum_expose_highpass: n_orb differs from the observation's");
-    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_expose_highpass: bad spectrum");
-    for (int64_t w = 0; w < n_wav; ++w)
-      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
-                   "prom_spectrum_expose_highpass: wavelengths must be finite and ascending");
-    const hipStream_t st = ctx->stream;
-    ex.last_wav = ex.last_R = nullptr;   // (the uploads may move the buffers the last call read)
-    upload(ex.wav, wav, n_wav, st);
-    upload(ex.R, R, (int64_t)n_orb * n_wav, st);
-    highpass_on(ctx, st, ex.wav.as<double>(), ex.R.as<double>(), n_wav, detrend, mom_out, n_used_out, model_out);
-  });
-}
-
-int32_t prom_highpass_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_highpass_kernel_ms: bad arguments");
-    if (!ex.set || !ex.hp_set || !ex.hp_ran || !ctx->obs.set || !ex.last_wav || ctx->obs.n_pix == 0 ||
-        (ex.hp_detrend && !ex.dt_set))
-      throw Error(PROM_E_STATE, "prom_highpass_kernel_ms: no high-pass call to repeat");
-    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
-    const hipStream_t st = ctx->stream;
-    // the filter works in place, so every repetition forms the unfiltered model again (untimed) before k_highpass
-    // (timed, the whole table)
-    double sum = 0.0;
-    for (int32_t r = 0; r < n_runs; ++r) {
-      highpass_model(ctx, st, ex.last_wav, ex.last_R, ex.last_n_wav, ex.hp_detrend, ctx->ev[0], ctx->ev[1]);
-      PROM_HIP(hipStreamSynchronize(st));
-      float ms = 0.0f;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      sum += ms;
-    }
-    ms_out[0] = sum / n_runs;
-  });
-}
-
-// ------------------------------------------------------------------------------ per-order moments
-int32_t prom_orders_set(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32_t* seg_first, const int32_t* perm,
-                        const uint8_t* keep) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    ex.od_set = ex.od_ran = false;
-    if (!ex.set || !ctx->obs.set || ctx->obs.n_orb != ex.n_orb)
-      throw Error(PROM_E_STATE, "prom_orders_set: no exposure table on the context (prom_expose_set)");
-    PROM_REQUIRE(n_pix == ctx->obs.n_pix, "prom_orders_set: n_pix differs from the observation's");
-    PROM_REQUIRE(n_seg >= 1 && seg_first && keep && (n_pix == 0 || perm), "prom_orders_set: orders missing");
-    if (n_pix == 0) {   // no pixel: no order can hold one; the calls give zeros
-      PROM_REQUIRE(n_seg == 1 && seg_first[0] == 0 && seg_first[1] == 0,
-                   "prom_orders_set: without pixels seg_first must be {0, 0}");
-    } else {
-      PROM_REQUIRE(n_seg <= n_pix && seg_first[0] == 0 && seg_first[n_seg] == n_pix,
-                   "prom_orders_set: seg_first must run from 0 to n_pix");
-      for (int32_t i = 0; i < n_seg; ++i)
-        PROM_REQUIRE(seg_first[i + 1] > seg_first[i], "prom_orders_set: seg_first must be strictly ascending");
-      std::vector<char> seen((size_t)n_pix, 0);
-      for (int32_t i = 0; i < n_pix; ++i) {
-        PROM_REQUIRE(perm[i] >= 0 && perm[i] < n_pix && !seen[(size_t)perm[i]],
-                     "prom_orders_set: perm must be a permutation of 0 .. n_pix - 1");
-        seen[(size_t)perm[i]] = 1;
-      }
-    }
-    for (int32_t i = 0; i < n_seg; ++i) PROM_REQUIRE(keep[i] <= 1, "prom_orders_set: keep must be 0 or 1");
-    const hipStream_t st = ctx->stream;
-    upload(ex.od_seg, seg_first, (int64_t)n_seg + 1, st);
-    upload(ex.od_perm, perm, (int64_t)n_pix, st);
-    upload(ex.od_keep, keep, (int64_t)n_seg, st);
-    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
-    ex.od_n_seg = n_seg;
-    ex.od_set = true;
-  });
-}
-
-// k_order_moments + k_order_totals over the final model in ex.model, in batches of whole trial groups under the scratch
-// cap (one group at least); a batch's records go to the caller's arrays when they are wanted (ev: events around the two
-// kernels of the first batch; data: as moments_launch's)
-static void orders_launch(prom_ctx* ctx, hipStream_t st, double* orec_mom_out, int64_t* orec_n_used_out,
-                          hipEvent_t* ev, const double* data = nullptr) {
-  prom::ExDev& ex = ctx->ex;
-  const int32_t n_pix = ctx->obs.n_pix, n_seg = ex.od_n_seg, n_groups = prom::od_groups(ex.n_trial);
-  const int32_t bg = prom::od_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, n_seg, n_groups);
-  const int32_t nb_max = std::min(bg * prom::kOdTrials, ex.n_trial);
-  ex.od_rec.ensure(sizeof(double) * (size_t)prom::od_record_doubles(ex.n_exp, nb_max, n_seg));
-  ex.od_tot.ensure(sizeof(double) * (size_t)prom::kOdTotals * ex.n_exp * ex.n_trial);
-  static const bool debug = std::getenv("PROM_DEBUG") != nullptr;
-  if (debug)
-    std::fprintf(stderr, "prom: per-order moments: %d trials in %d groups, %d batches of up to %d groups, %d orders\n",
-                 ex.n_trial, n_groups, (n_groups + bg - 1) / bg, bg, n_seg);
-  const bool want = orec_mom_out || orec_n_used_out;
-  std::vector<double> host;
-  if (want) host.resize((size_t)prom::od_record_doubles(ex.n_exp, nb_max, n_seg));
-  for (int32_t g = 0; g < n_groups; g += bg) {
-    const int32_t j_first = prom::od_group_first(g), nb = std::min(nb_max, ex.n_trial - j_first);
-    prom::launch_order_moments(st, ex.model.as<double>(), ex.flag.as<uint8_t>(), data ? data : ex.data.as<double>(),
-                               ex.ivar.as<double>(), ex.od_seg.as<int32_t>(), ex.od_perm.as<int32_t>(), n_pix, ex.n_exp,
-                               ex.n_trial, j_first, nb, n_seg, ex.od_rec.as<double>(), ev && g == 0 ? ev[0] : nullptr,
-                               ev && g == 0 ? ev[1] : nullptr);
-    prom::launch_order_totals(st, ex.od_rec.as<double>(), ex.od_keep.as<uint8_t>(), ex.n_exp, ex.n_trial, j_first, nb,
-                              n_seg, ex.od_tot.as<double>(), ev && g == 0 ? ev[2] : nullptr,
-                              ev && g == 0 ? ev[3] : nullptr);
-    if (!want) continue;
-    download(host.data(), ex.od_rec, prom::od_record_doubles(ex.n_exp, nb, n_seg), st);
-    PROM_HIP(hipStreamSynchronize(st));   // (the next batch writes the same buffer)
-    for (int32_t e = 0; e < ex.n_exp; ++e)
-      for (int32_t jb = 0; jb < nb; ++jb)
-        for (int32_t s = 0; s < n_seg; ++s) {
-          const double* rec = host.data() + prom::od_record(e, jb, s, nb, n_seg);
-          const int64_t to = ((int64_t)e * ex.n_trial + j_first + jb) * n_seg + s;
-          if (orec_mom_out) std::copy(rec, rec + 7, orec_mom_out + 7 * to);
-          if (orec_n_used_out) std::memcpy(orec_n_used_out + to, rec + 7, sizeof(int64_t));
-        }
-  }
-}
-
-// the shared tail of the two per-order calls, on stream st
-static void orders_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav,
-                      int32_t highpass, int32_t detrend, double* mom_out, int64_t* n_used_out, double* orec_mom_out,
-                      int64_t* orec_n_used_out, double* tot_out, double* model_out) {
-  prom::ExDev& ex = ctx->ex;
-  const int32_t n_pix = ctx->obs.n_pix, n_seg = ex.od_n_seg;
-  const int64_t n = (int64_t)ex.n_exp * ex.n_trial;
-  ex.od_ran = false;
-  if (n_pix == 0) {   // no pixel: every moment, record and total 0 and no model value
-    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
-    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
-    if (orec_mom_out) std::fill(orec_mom_out, orec_mom_out + 7 * n * n_seg, 0.0);
-    if (orec_n_used_out) std::fill(orec_n_used_out, orec_n_used_out + n * n_seg, (int64_t)0);
-    if (tot_out) std::fill(tot_out, tot_out + prom::kOdTotals * n, 0.0);
-    return;
-  }
-  const bool want_orders = orec_mom_out || orec_n_used_out || tot_out;
-  if (!mom_out && !n_used_out && !want_orders && !model_out) return;
-  // (before anything is launched)
-  if (prom::od_workgroups(ex.n_exp, 1, n_seg) > (((int64_t)1 << 31) - 1))
-    throw Error(PROM_E_ARG, "k_order_moments: n_exp n_seg too large for one launch");
-  if (highpass && prom::hp_workgroups(n, ex.hp_n_seg) > (((int64_t)1 << 31) - 1))
-    throw Error(PROM_E_ARG, "k_highpass: n_exp n_trial n_seg too large for one launch");
-  const double nan = std::nan("");
-  const int64_t nm = n * n_pix;
-  ex.q.ensure(sizeof(double) * (size_t)n_wav);
-  try {   // the whole table's model is resident at once: it is not batched
-    ex.model.ensure(sizeof(double) * (size_t)nm);
-  } catch (const Error& err) {
-    throw Error(err.code, std::string(err.what()) + ": the per-order moments keep the model of all " +
-                              std::to_string(ex.n_trial) + " trials in device memory; give fewer trials per call");
-  }
-  ex.flag.ensure((size_t)ex.n_trial * n_pix);
-  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
-  // the final model: k_expose without moments, then the filters asked for, as highpass_model / detrend_model run them
-  expose_launch(ctx, st, wav, R, (int32_t)n_wav, false, ex.model.as<double>(), nullptr, nullptr);
-  if (highpass)
-    prom::launch_highpass(st, ex.model.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(),
-                          ex.hp_g.as<double>(), ex.hp_half, ex.hp_den, ex.hp_mode, n, ex.hp_n_seg, n_pix, nullptr,
-                          nullptr);
-  if (detrend)
-    prom::launch_detrend(st, ex.model.as<double>(), ex.U.as<double>(), ex.W.as<double>(), ex.flag.as<uint8_t>(),
-                         ex.n_exp, ex.n_comp, ex.n_trial, n_pix, nullptr, nullptr);
-  else
-    PROM_HIP(hipMemsetAsync(ex.flag.as<uint8_t>(), 1, (size_t)ex.n_trial * n_pix, st));
-  if (mom_out || n_used_out) moments_launch(ctx, st, nullptr, nullptr);
-  ex.last_wav = wav;
-  ex.last_R = R;
-  ex.last_n_wav = (int32_t)n_wav;
-  ex.dt_ran = ex.hp_ran = false;
-  ex.od_ran = true;
-  if (want_orders) orders_launch(ctx, st, orec_mom_out, orec_n_used_out, nullptr);
-  if (mom_out) download(mom_out, ex.mom, 7 * n, st);
-  if (n_used_out) download(n_used_out, ex.n_used, n, st);
-  if (tot_out) download(tot_out, ex.od_tot, prom::kOdTotals * n, st);
-  if (model_out) download(model_out, ex.model, nm, st);
-  PROM_HIP(hipStreamSynchronize(st));
-}
-
-static void orders_check(prom_ctx* ctx, const char* who, int32_t highpass, int32_t detrend) {
-  expose_check(ctx, who);
-  if (!ctx->ex.od_set)
-    throw Error(PROM_E_STATE, std::string(who) + ": no orders on the context (prom_orders_set; a later "
-                                                 "prom_expose_set, or whatever drops the exposure table, drops them)");
-  if (highpass != 0 && highpass != 1) throw Error(PROM_E_ARG, std::string(who) + ": highpass must be 0 or 1");
-  if (detrend != 0 && detrend != 1) throw Error(PROM_E_ARG, std::string(who) + ": detrend must be 0 or 1");
-  if (highpass && !ctx->ex.hp_set)
-    throw Error(PROM_E_STATE, std::string(who) + ": highpass = 1 without a high-pass on the context (prom_highpass_set)");
-  if (detrend && !ctx->ex.dt_set)
-    throw Error(PROM_E_STATE, std::string(who) + ": detrend = 1 without a filter on the context (prom_detrend_set)");
-}
-
-int32_t prom_transit_expose_orders(prom_ctx* ctx, int32_t highpass, int32_t detrend, double* mom_out,
-                                   int64_t* n_used_out, double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out,
-                                   double* model_out) {
-  return guarded(ctx, [&] {
-    prom::TransitDev& tr = ctx->tr;
-    orders_check(ctx, "prom_transit_expose_orders", highpass, detrend);
-    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_expose_orders: no completed run");
-    if (ctx->ex.n_orb != tr.n_orb)
-      throw Error(PROM_E_STATE, "prom_transit_expose_orders: the exposure table has another n_orb");
-    orders_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, highpass,
-              detrend, mom_out, n_used_out, orec_mom_out, orec_n_used_out, tot_out, model_out);
-  });
-}
-
-int32_t prom_spectrum_expose_orders(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
-                                    int32_t highpass, int32_t detrend, double* mom_out, int64_t* n_used_out,
-                                    double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out,
-                                    double* model_out) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    orders_check(ctx, "prom_spectrum_expose_orders", highpass, detrend);
-    PROM_REQUIRE(n_orb == ex.n_orb, "prom_spectrum_expose_orders: n_orb differs from the observation's");
-    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_expose_orders: bad spectrum");
-    for (int64_t w = 0; w < n_wav; ++w)
-      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
-                   "prom_spectrum_expose_orders: wavelengths must be finite and ascending");
-    const hipStream_t st = ctx->stream;
-    ex.last_wav = ex.last_R = nullptr;   // (the uploads may move the buffers the last call read)
-    ex.od_ran = false;
-    upload(ex.wav, wav, n_wav, st);
-    upload(ex.R, R, (int64_t)n_orb * n_wav, st);
-    orders_on(ctx, st, ex.wav.as<double>(), ex.R.as<double>(), n_wav, highpass, detrend, mom_out, n_used_out,
-              orec_mom_out, orec_n_used_out, tot_out, model_out);
-  });
-}
-
-int32_t prom_orders_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_orders_kernel_ms: bad arguments");
-    if (!ex.set || !ex.od_set || !ex.od_ran || !ctx->obs.set || ctx->obs.n_pix == 0)
-      throw Error(PROM_E_STATE, "prom_orders_kernel_ms: no per-order call to repeat");
-    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
-    const hipStream_t st = ctx->stream;
-    // the two kernels read the final model and the flags the last call left; the first batch, scaled to the table by
-    // trial count
-    const int32_t n_groups = prom::od_groups(ex.n_trial);
-    const int32_t bg = prom::od_batch_groups(ctx->vmap_scratch_bytes, ex.n_exp, ex.od_n_seg, n_groups);
-    const double scale = (double)ex.n_trial / (double)std::min(bg * prom::kOdTrials, ex.n_trial);
-    double sum[2] = {0.0, 0.0};
-    for (int32_t r = 0; r < n_runs; ++r) {
-      orders_launch(ctx, st, nullptr, nullptr, ctx->ev);
-      PROM_HIP(hipStreamSynchronize(st));
-      float ms = 0.0f;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      sum[0] += ms;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-      sum[1] += ms;
-    }
-    ms_out[0] = scale * sum[0] / n_runs;
-    ms_out[1] = scale * sum[1] / n_runs;
-  });
-}
-
-// ------------------------------------------------------------------------------ broadened spectra
-int32_t prom_broaden_set(prom_ctx* ctx, int32_t n_k, double b0, double s, const double* K) {
-  return guarded(ctx, [&] {
-    prom::BrDev& br = ctx->br;
-    br.set = false;
-    br.current = false;   // R_b was formed with the kernel that leaves
-    br.last_wav = br.last_q = br.last_R = nullptr;
-    br.last_out = nullptr;
-    if (n_k == 0) return;
-    PROM_REQUIRE(n_k >= 2 && n_k <= prom::kBrMaxNodes && K, "prom_broaden_set: n_k must be 0 or lie in [2, 1025]");
-    PROM_REQUIRE(obs_finite(b0), "prom_broaden_set: b0 must be finite");
-    PROM_REQUIRE(obs_finite(s) && s > 0.0, "prom_broaden_set: s must be finite and > 0");
-    bool any = false;
-    for (int32_t i = 0; i < n_k; ++i) {
-      PROM_REQUIRE(obs_finite(K[i]) && K[i] >= 0.0, "prom_broaden_set: K must be finite and >= 0");
-      any = any || K[i] > 0.0;
-    }
-    PROM_REQUIRE(any, "prom_broaden_set: K must not be all zero");
-    std::vector<prom::BrRec> rec((size_t)n_k);
-    for (int32_t i = 0; i < n_k; ++i) rec[i] = prom::BrRec{K[i], i + 1 < n_k ? K[i + 1] - K[i] : 0.0};
-    const hipStream_t st = ctx->stream;
-    for (auto t : ctx->streams) PROM_HIP(hipStreamSynchronize(t));   // (a launch in flight may read the old records)
-    upload(br.rec, rec.data(), n_k, st);
-    PROM_HIP(hipStreamSynchronize(st));   // the host array is read during the call only
-    br.n_k = n_k;
-    br.b0 = b0;
-    br.s = s;
-    br.set = true;
-  });
-}
-
-// q of the whole grid and k_broaden on stream st (ev: events around k_broaden)
-static void broaden_launch(prom_ctx* ctx, hipStream_t st, const double* wav, double* q, const double* R, int32_t n_wav,
-                           int32_t n_orb, double* out) {
-  prom::BrDev& br = ctx->br;
-  const double nan = std::nan("");
-  prom::launch_observe_q(st, wav, n_wav, nan, nan, q);
-  prom::launch_broaden(st, wav, q, R, n_wav, n_orb, br.rec.as<prom::BrRec>(), prom::BrKern{br.b0, br.s, br.n_k}, out,
-                       nullptr, nullptr);
-  br.last_wav = wav;
-  br.last_q = q;
-  br.last_R = R;
-  br.last_out = out;
-  br.last_n_wav = n_wav;
-  br.last_n_orb = n_orb;
-}
-
-int32_t prom_spectrum_broaden(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
-                              double* Rb_out) {
-  return guarded(ctx, [&] {
-    prom::BrDev& br = ctx->br;
-    if (!br.set) throw Error(PROM_E_STATE, "prom_spectrum_broaden: no kernel on the context (prom_broaden_set)");
-    PROM_REQUIRE(n_orb >= 1 && n_orb <= 65535, "prom_spectrum_broaden: bad n_orb");
-    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R && Rb_out, "prom_spectrum_broaden: bad spectrum");
-    for (int64_t w = 0; w < n_wav; ++w)
-      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
-                   "prom_spectrum_broaden: wavelengths must be finite and ascending");
-    PROM_REQUIRE(wav[0] > 0.0 && obs_finite(1.0 / wav[0]),
-                 "prom_spectrum_broaden: wavelengths must be > 0 (and 1 / wav finite)");
-    const hipStream_t st = ctx->stream;
-    const int64_t n = (int64_t)n_orb * n_wav;
-    br.last_wav = br.last_q = br.last_R = nullptr;   // (the uploads may move the buffers the last call read)
-    br.last_out = nullptr;
-    upload(br.wav, wav, n_wav, st);
-    upload(br.R, R, n, st);
-    br.sq.ensure(sizeof(double) * (size_t)n_wav);
-    br.out.ensure(sizeof(double) * (size_t)n);
-    broaden_launch(ctx, st, br.wav.as<double>(), br.sq.as<double>(), br.R.as<double>(), (int32_t)n_wav, n_orb,
-                   br.out.as<double>());
-    download(Rb_out, br.out, n, st);
-    PROM_HIP(hipStreamSynchronize(st));
-  });
-}
-
-int32_t prom_transit_broaden(prom_ctx* ctx) {
-  return guarded(ctx, [&] {
-    prom::TransitDev& tr = ctx->tr;
-    prom::BrDev& br = ctx->br;
-    if (!br.set) throw Error(PROM_E_STATE, "prom_transit_broaden: no kernel on the context (prom_broaden_set)");
-    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_broaden: no completed run");
-    const hipStream_t st = ctx->streams[tr.last];
-    // R_b and q are one buffer each: an earlier broaden on another stream must be through with them
-    if (br.stream && br.stream != st) PROM_HIP(hipStreamSynchronize(br.stream));
-    const size_t bytes = sizeof(double) * (size_t)tr.n_orb * (size_t)tr.n_wav;
-    if (bytes > br.Rb.cap || sizeof(double) * (size_t)tr.n_wav > br.q.cap) {
-      // the buffers move: nothing may read the old ones any more, and no measurement aid may repeat a call on them
-      for (auto t : ctx->streams) PROM_HIP(hipStreamSynchronize(t));
-      const double* old = br.Rb.as<double>();
-      if (old && ctx->obs.last_R == old) ctx->obs.last_wav = ctx->obs.last_R = nullptr;
-      if (old && ctx->vm.last_R == old) ctx->vm.last_wav = ctx->vm.last_R = nullptr;
-      if (old && ctx->ex.last_R == old) {
-        ctx->ex.last_wav = ctx->ex.last_R = nullptr;
-        ctx->ex.dt_ran = ctx->ex.hp_ran = ctx->ex.od_ran = false;
-      }
-      br.last_wav = br.last_q = br.last_R = nullptr;
-      br.last_out = nullptr;
-    }
-    br.current = false;
-    br.q.ensure(sizeof(double) * (size_t)tr.n_wav);
-    br.Rb.ensure(bytes);
-    broaden_launch(ctx, st, tr.wav.as<double>(), br.q.as<double>(), tr.slot[tr.last].R.as<double>(), (int32_t)tr.n_wav,
-                   tr.n_orb, br.Rb.as<double>());
-    br.stream = st;
-    br.current = true;
-  });
-}
-
-int32_t prom_transit_broadened(prom_ctx* ctx, double* Rb_out) {
-  return guarded(ctx, [&] {
-    prom::TransitDev& tr = ctx->tr;
-    prom::BrDev& br = ctx->br;
-    if (!tr.ran || !br.current)
-      throw Error(PROM_E_STATE, "prom_transit_broadened: no broadened spectrum of the last run (prom_transit_broaden)");
-    PROM_REQUIRE(Rb_out, "prom_transit_broadened: null output");
-    const hipStream_t st = br.stream;
-    download(Rb_out, br.Rb, (int64_t)tr.n_orb * tr.n_wav, st);
-    PROM_HIP(hipStreamSynchronize(st));
-  });
-}
-
-int32_t prom_broaden_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
-  return guarded(ctx, [&] {
-    prom::BrDev& br = ctx->br;
-    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_broaden_kernel_ms: bad arguments");
-    if (!br.set || !br.last_wav) throw Error(PROM_E_STATE, "prom_broaden_kernel_ms: no broaden call to repeat");
-    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
-    const hipStream_t st = ctx->stream;
-    double sum = 0.0;
-    for (int32_t r = 0; r < n_runs; ++r) {
-      prom::launch_broaden(st, br.last_wav, br.last_q, br.last_R, br.last_n_wav, br.last_n_orb,
-                           br.rec.as<prom::BrRec>(), prom::BrKern{br.b0, br.s, br.n_k}, br.last_out, ctx->ev[0],
-                           ctx->ev[1]);
-      PROM_HIP(hipStreamSynchronize(st));
-      float ms = 0.0f;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      sum += ms;
-    }
-    *ms_out = sum / n_runs;
-  });
-}
-
-// ------------------------------------------------------------------------------ injection and SYSREM
-int32_t prom_sysrem_set(prom_ctx* ctx, int32_t n_exp, int32_t n_pix, const double* raw) {
-  return guarded(ctx, [&] {
-    prom::SyDev& sy = ctx->sy;
-    sy.set = false;
-    sy.last_source = 0;
-    if (!ctx->ex.set || !ctx->obs.set || ctx->obs.n_orb != ctx->ex.n_orb)
-      throw Error(PROM_E_STATE, "prom_sysrem_set: no exposure table on the context (prom_expose_set)");
-    PROM_REQUIRE(n_exp == ctx->ex.n_exp && n_pix == ctx->obs.n_pix,
-                 "prom_sysrem_set: raw must be [n_exp][n_pix] of the exposure table");
-    PROM_REQUIRE(n_exp <= prom::kSyMaxExp, "prom_sysrem_set: more than 4096 exposures");
-    const int64_t n = (int64_t)n_exp * n_pix;
-    PROM_REQUIRE(n == 0 || raw, "prom_sysrem_set: raw missing");
-    const hipStream_t st = ctx->stream;
-    upload(sy.raw, raw, n, st);
-    PROM_HIP(hipStreamSynchronize(st));   // the host array is read during the call only
-    sy.n_exp = n_exp;
-    sy.n_pix = n_pix;
-    sy.set = true;
-  });
-}
-
-namespace {
-
-// what a clean / inject call asks for (source 1: clean, 2: the last run's R, 3: a caller's spectrum)
-struct SyCall {
-  int32_t source, trial, highpass, n_comp, n_iter, ones;
-  double scale;
-};
-
-void sysrem_check(prom_ctx* ctx, const char* who, const SyCall& c) {
-  const std::string w(who);
-  if (!ctx->ex.set || !ctx->obs.set || ctx->obs.n_orb != ctx->ex.n_orb)
-    throw Error(PROM_E_STATE, w + ": no exposure table on the context (prom_expose_set; a later prom_observe_set or a "
-                                  "prom_transit_set with another n_orb drops it)");
-  if (!ctx->sy.set)
-    throw Error(PROM_E_STATE, w + ": no raw exposures on the context (prom_sysrem_set; a later prom_expose_set, or "
-                                  "whatever drops the exposure table, drops them)");
-  if (c.highpass != 0 && c.highpass != 1) throw Error(PROM_E_ARG, w + ": highpass must be 0 or 1");
-  if (c.ones != 0 && c.ones != 1) throw Error(PROM_E_ARG, w + ": ones must be 0 or 1");
-  if (c.n_comp < 0 || c.n_comp + c.ones < 1 || c.n_comp + c.ones > prom::kSyMaxComp)
-    throw Error(PROM_E_ARG, w + ": n_comp >= 0 and 1 <= n_comp + ones <= 16");
-  if (c.n_iter < 1) throw Error(PROM_E_ARG, w + ": n_iter must be >= 1");
-  if (c.source != 1) {
-    if (c.trial < 0 || c.trial >= ctx->ex.n_trial) throw Error(PROM_E_ARG, w + ": trial outside [0, n_trial)");
-    if (!std::isfinite(c.scale)) throw Error(PROM_E_ARG, w + ": scale must be finite");
-  }
-  if (c.highpass && !ctx->ex.hp_set)
-    throw Error(PROM_E_STATE, w + ": highpass = 1 without a high-pass on the context (prom_highpass_set)");
-}
-
-// the shared tail of the clean / inject calls on stream st (ev: six events around the injection, the high-pass and
-// SYSREM, and the call runs even without an output; wait = false: a recover call goes on on the same stream, so the call
-// runs whatever the outputs and does not wait)
-void sysrem_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, const SyCall& c,
-               double* U_out, double* cleaned_out, double* injected_out, hipEvent_t* ev, bool wait = true) {
-  prom::SyDev& sy = ctx->sy;
-  prom::ExDev& ex = ctx->ex;
-  const prom::ObsDev& ob = ctx->obs;
-  const int32_t n_exp = sy.n_exp, n_pix = sy.n_pix, n_cols = c.n_comp + c.ones;
-  const int64_t n = (int64_t)n_exp * n_pix;
-  if (n_pix == 0) {   // no pixel: every component ends at once
-    if (U_out)
-      for (int32_t e = 0; e < n_exp; ++e)
-        for (int32_t k = 0; k < n_cols; ++k) U_out[prom::sy_u(e, k, n_cols)] = (c.ones && k == 0) ? 1.0 : 0.0;
-    return;
-  }
-  if (wait && !ev && !U_out && !cleaned_out && !injected_out) return;
-  if (ctx->rc.last == 2) ctx->rc.last = 0;   // (U may move or change its shape)
-  if (c.highpass && prom::hp_workgroups(n_exp, ex.hp_n_seg) > (((int64_t)1 << 31) - 1))   // (before anything is launched)
-    throw Error(PROM_E_ARG, "k_highpass: n_exp n_seg too large for one launch");
-  const int64_t pitch = prom::sy_pitch(n_pix);
-  sy.D.ensure(sizeof(double) * (size_t)n);
-  sy.out.ensure(sizeof(double) * (size_t)n);
-  sy.r.ensure(sizeof(double) * (size_t)(n_exp * pitch));
-  sy.w.ensure(sizeof(double) * (size_t)(n_exp * pitch));
-  sy.a.ensure(sizeof(double) * (size_t)n_exp);
-  sy.ended.ensure(sizeof(int32_t) * (prom::kSyMaxComp + 1));
-  sy.part.ensure(2 * sizeof(double) * (size_t)n_exp * prom::sy_tiles(n_pix));
-  sy.U.ensure(sizeof(double) * (size_t)n_exp * n_cols);
-  if (ev) PROM_HIP(hipEventRecord(ev[0], st));
-  if (c.source != 1) {
-    // the model of trial `trial` alone: its factors as a table of one trial, through k_expose unchanged
-    const double nan = std::nan("");
-    sy.q.ensure(sizeof(double) * (size_t)n_wav);
-    sy.Fj.ensure(sizeof(double) * (size_t)n_exp * ex.n_tap);
-    sy.model.ensure(sizeof(double) * (size_t)n);
-    sy.epart.ensure(sizeof(double) * (size_t)prom::vm_part_doubles(n_exp, 1, prom::vm_chunks(n_pix)));
-    prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, sy.q.as<double>());
-    prom::launch_sysrem_gather(st, ex.F.as<double>(), sy.Fj.as<double>(), n_exp, ex.n_trial, ex.n_tap, c.trial);
-    prom::launch_expose(st, wav, sy.q.as<double>(), R, (int32_t)n_wav, ob.lam.as<double>(), ob.sig.as<double>(), ob.k,
-                        ex.row.as<int32_t>(), ex.a.as<double>(), sy.Fj.as<double>(), ex.data.as<double>(),
-                        ex.ivar.as<double>(), n_pix, n_exp, 1, ex.n_tap, 0, 1, sy.epart.as<double>(),
-                        sy.model.as<double>(), nullptr, nullptr);
-    prom::launch_inject(st, sy.raw.as<double>(), sy.model.as<double>(), c.scale, sy.D.as<double>(), n);
-  } else {
-    PROM_HIP(hipMemcpyAsync(sy.D.p, sy.raw.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-  }
-  if (ev) PROM_HIP(hipEventRecord(ev[1], st));
-  if (ev) PROM_HIP(hipEventRecord(ev[2], st));
-  if (c.highpass)
-    prom::launch_highpass(st, sy.D.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(), ex.hp_g.as<double>(),
-                          ex.hp_half, ex.hp_den, ex.hp_mode, n_exp, ex.hp_n_seg, n_pix, nullptr, nullptr);
-  if (ev) PROM_HIP(hipEventRecord(ev[3], st));
-  if (ev) PROM_HIP(hipEventRecord(ev[4], st));
-  prom::launch_sysrem(st, sy.D.as<double>(), ex.ivar.as<double>(), sy.r.as<double>(), sy.w.as<double>(),
-                      sy.a.as<double>(), sy.ended.as<int32_t>(), sy.part.as<double>(), sy.U.as<double>(),
-                      sy.out.as<double>(), n_exp, n_pix, c.n_comp, c.n_iter, c.ones);
-  if (ev) PROM_HIP(hipEventRecord(ev[5], st));
-  sy.last_source = c.source;
-  sy.last_trial = c.trial;
-  sy.last_scale = c.scale;
-  sy.last_highpass = c.highpass;
-  sy.last_n_comp = c.n_comp;
-  sy.last_n_iter = c.n_iter;
-  sy.last_ones = c.ones;
-  sy.last_n_wav = n_wav;
-  if (U_out) download(U_out, sy.U, (int64_t)n_exp * n_cols, st);
-  if (cleaned_out) download(cleaned_out, sy.out, n, st);
-  if (injected_out) download(injected_out, sy.D, n, st);
-  if (wait) PROM_HIP(hipStreamSynchronize(st));
-}
-
-}  // namespace
-
-int32_t prom_sysrem_clean(prom_ctx* ctx, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out,
-                          double* cleaned_out, double* injected_out) {
-  return guarded(ctx, [&] {
-    const SyCall c{1, 0, highpass, n_comp, n_iter, ones, 0.0};
-    sysrem_check(ctx, "prom_sysrem_clean", c);
-    sysrem_on(ctx, ctx->stream, nullptr, nullptr, 0, c, U_out, cleaned_out, injected_out, nullptr);
-  });
-}
-
-int32_t prom_transit_inject(prom_ctx* ctx, int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter,
-                            int32_t ones, double* U_out, double* cleaned_out, double* injected_out) {
-  return guarded(ctx, [&] {
-    prom::TransitDev& tr = ctx->tr;
-    const SyCall c{2, trial, highpass, n_comp, n_iter, ones, scale};
-    sysrem_check(ctx, "prom_transit_inject", c);
-    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_inject: no completed run");
-    if (ctx->ex.n_orb != tr.n_orb)
-      throw Error(PROM_E_STATE, "prom_transit_inject: the exposure table has another n_orb");
-    // the last run's stream orders the injection after it
-    sysrem_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, c, U_out, cleaned_out,
-              injected_out, nullptr);
-  });
-}
-
-int32_t prom_spectrum_inject(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
-                             int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones,
-                             double* U_out, double* cleaned_out, double* injected_out) {
-  return guarded(ctx, [&] {
-    prom::SyDev& sy = ctx->sy;
-    const SyCall c{3, trial, highpass, n_comp, n_iter, ones, scale};
-    sysrem_check(ctx, "prom_spectrum_inject", c);
-    PROM_REQUIRE(n_orb == ctx->ex.n_orb, "prom_spectrum_inject: n_orb differs from the observation's");
-    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_inject: bad spectrum");
-    for (int64_t w = 0; w < n_wav; ++w)
-      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
-                   "prom_spectrum_inject: wavelengths must be finite and ascending");
-    const hipStream_t st = ctx->stream;
-    sy.last_source = 0;   // (the uploads may move the buffers the last call read)
-    upload(sy.wav, wav, n_wav, st);
-    upload(sy.R, R, (int64_t)n_orb * n_wav, st);
-    sy.last_n_orb = n_orb;
-    sysrem_on(ctx, st, sy.wav.as<double>(), sy.R.as<double>(), n_wav, c, U_out, cleaned_out, injected_out, nullptr);
-  });
-}
-
-int32_t prom_sysrem_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
-  return guarded(ctx, [&] {
-    prom::SyDev& sy = ctx->sy;
-    prom::TransitDev& tr = ctx->tr;
-    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_sysrem_kernel_ms: bad arguments");
-    const bool table = ctx->ex.set && ctx->obs.set && ctx->obs.n_orb == ctx->ex.n_orb && sy.set && sy.n_pix > 0;
-    if (!table || sy.last_source == 0 || (sy.last_highpass && !ctx->ex.hp_set) ||
-        (sy.last_source == 2 && (!tr.ran || ctx->ex.n_orb != tr.n_orb || tr.n_wav != sy.last_n_wav)) ||
-        (sy.last_source == 3 && sy.last_n_orb != ctx->ex.n_orb))
-      throw Error(PROM_E_STATE, "prom_sysrem_kernel_ms: no clean or inject call to repeat");
-    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
-    const hipStream_t st = ctx->stream;
-    const SyCall c{sy.last_source, sy.last_trial, sy.last_highpass, sy.last_n_comp, sy.last_n_iter, sy.last_ones,
-                   sy.last_scale};
-    const double* wav = c.source == 2 ? tr.wav.as<double>() : sy.wav.as<double>();
-    const double* R = c.source == 2 ? transit_R(ctx) : sy.R.as<double>();
-    double sum[3] = {0.0, 0.0, 0.0};
-    for (int32_t r = 0; r < n_runs; ++r) {
-      sysrem_on(ctx, st, wav, R, sy.last_n_wav, c, nullptr, nullptr, nullptr, ctx->ev);
-      float ms = 0.0f;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
-      sum[0] += ms;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      sum[1] += ms;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-      sum[2] += ms;
-    }
-    ms_out[0] = sum[0] / n_runs;
-    ms_out[1] = c.source != 1 ? sum[1] / n_runs : std::nan("");
-    ms_out[2] = c.highpass ? sum[2] / n_runs : std::nan("");
-  });
-}
-
-// ------------------------------------------------------------------------------ the filter's weights and the recovery
-int32_t prom_filter_weights(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, int32_t n_pix, const double* U,
-                            const double* ivar, double* W_out) {
-  return guarded(ctx, [&] {
-    prom::RcDev& rc = ctx->rc;
-    PROM_REQUIRE(n_comp >= 1 && n_comp <= prom::kDtMaxComp, "prom_filter_weights: n_comp must lie in [1, 16]");
-    PROM_REQUIRE(n_exp >= 1 && n_pix >= 0, "prom_filter_weights: n_exp must be >= 1 and n_pix >= 0");
-    const int64_t nu = (int64_t)n_exp * n_comp, ni = (int64_t)n_exp * n_pix, nw = nu * n_pix;
-    PROM_REQUIRE(U && (n_pix == 0 || (ivar && W_out)), "prom_filter_weights: U, ivar or W_out missing");
-    for (int64_t i = 0; i < nu; ++i) PROM_REQUIRE(obs_finite(U[i]), "prom_filter_weights: U must be finite");
-    if (n_pix == 0) return;
-    const hipStream_t st = ctx->stream;
-    upload(rc.fU, U, nu, st);
-    upload(rc.fivar, ivar, ni, st);
-    rc.fW.ensure(sizeof(double) * (size_t)nw);
-    prom::launch_filter_weights(st, rc.fU.as<double>(), rc.fivar.as<double>(), rc.fW.as<double>(), n_exp, n_comp, n_pix,
-                                nullptr, nullptr);
-    download(W_out, rc.fW, nw, st);
-    PROM_HIP(hipStreamSynchronize(st));
-  });
-}
-
-int32_t prom_detrend_build(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, const double* U, double* W_out) {
-  return guarded(ctx, [&] {
-    prom::ExDev& ex = ctx->ex;
-    ex.dt_set = ex.dt_ran = false;
-    if (ctx->rc.last == 1) ctx->rc.last = 0;
-    if (!ex.set || !ctx->obs.set || ctx->obs.n_orb != ex.n_orb)
-      throw Error(PROM_E_STATE, "prom_detrend_build: no exposure table on the context (prom_expose_set)");
-    PROM_REQUIRE(n_exp == ex.n_exp, "prom_detrend_build: n_exp differs from the exposure table's");
-    PROM_REQUIRE(n_comp >= 1 && n_comp <= prom::kDtMaxComp, "prom_detrend_build: n_comp must lie in [1, 16]");
-    const int32_t n_pix = ctx->obs.n_pix;
-    const int64_t nu = (int64_t)n_exp * n_comp, nw = nu * n_pix;
-    PROM_REQUIRE(U, "prom_detrend_build: U missing");
-    for (int64_t i = 0; i < nu; ++i) PROM_REQUIRE(obs_finite(U[i]), "prom_detrend_build: U must be finite");
-    const hipStream_t st = ctx->stream;
-    upload(ex.U, U, nu, st);
-    ex.W.ensure(sizeof(double) * (size_t)std::max<int64_t>(nw, 1));
-    prom::launch_filter_weights(st, ex.U.as<double>(), ex.ivar.as<double>(), ex.W.as<double>(), n_exp, n_comp, n_pix,
-                                nullptr, nullptr);
-    if (W_out) download(W_out, ex.W, nw, st);
-    PROM_HIP(hipStreamSynchronize(st));   // the host array is read during the call only
-    ex.n_comp = n_comp;
-    ex.dt_set = true;
-    if (n_pix > 0) {
-      ctx->rc.last = 1;
-      ctx->rc.last_n_comp = n_comp;
-    }
-  });
-}
-
-int32_t prom_filter_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
-  return guarded(ctx, [&] {
-    prom::RcDev& rc = ctx->rc;
-    prom::ExDev& ex = ctx->ex;
-    PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_filter_kernel_ms: bad arguments");
-    const bool table = ex.set && ctx->obs.set && ctx->obs.n_orb == ex.n_orb && ctx->obs.n_pix > 0;
-    const bool built = rc.last == 1 && ex.dt_set && ex.n_comp == rc.last_n_comp;
-    const bool recovered = rc.last == 2 && ctx->sy.set && ctx->sy.last_source != 0 &&
-                           ctx->sy.last_n_comp + ctx->sy.last_ones == rc.last_n_comp;
-    if (!table || !(built || recovered))
-      throw Error(PROM_E_STATE, "prom_filter_kernel_ms: no build or recover call to repeat");
-    for (auto st : ctx->streams) PROM_HIP(hipStreamSynchronize(st));
-    const hipStream_t st = ctx->stream;
-    // the kernel writes the W it wrote before, from the same inputs: the same bits
-    const double* U = built ? ex.U.as<double>() : ctx->sy.U.as<double>();
-    double* W = built ? ex.W.as<double>() : rc.W.as<double>();
-    double sum = 0.0;
-    for (int32_t r = 0; r < n_runs; ++r) {
-      prom::launch_filter_weights(st, U, ex.ivar.as<double>(), W, ex.n_exp, rc.last_n_comp, ctx->obs.n_pix, ctx->ev[0],
-                                  ctx->ev[1]);
-      PROM_HIP(hipStreamSynchronize(st));
-      float ms = 0.0f;
-      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      sum += ms;
-    }
-    ms_out[0] = sum / n_runs;
-  });
-}
-
-namespace {
-
-void recover_check(prom_ctx* ctx, const char* who, const SyCall& c, int32_t orders) {
-  const std::string w(who);
-  sysrem_check(ctx, who, c);
-  if (orders != 0 && orders != 1) throw Error(PROM_E_ARG, w + ": orders must be 0 or 1");
-  if (orders && !ctx->ex.od_set)
-    throw Error(PROM_E_STATE, w + ": orders = 1 without orders on the context (prom_orders_set)");
-}
-
-// the shared tail of the two recover calls on stream st: the inject call's steps, W of (U, ivar), then the chain of
-// the per-order call (highpass, detrend = 1) with the cleaned data in the place of the table's and (U, W) in the place
-// of the resident filter
-void recover_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, const SyCall& c,
-                int32_t orders, double* mom_out, int64_t* n_used_out, double* orec_mom_out, int64_t* orec_n_used_out,
-                double* tot_out, double* U_out, double* model_out) {
-  prom::ExDev& ex = ctx->ex;
-  prom::SyDev& sy = ctx->sy;
-  prom::RcDev& rc = ctx->rc;
-  const int32_t n_pix = ctx->obs.n_pix, n_exp = ex.n_exp, n_cols = c.n_comp + c.ones;
-  const int32_t n_seg = orders ? ex.od_n_seg : 0;
-  const int64_t n = (int64_t)n_exp * ex.n_trial;
-  if (n_pix == 0) {   // no pixel: the inject call's U, every moment, record and total 0 and no model value
-    sysrem_on(ctx, st, wav, R, n_wav, c, U_out, nullptr, nullptr, nullptr);
-    if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
-    if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
-    if (orders && orec_mom_out) std::fill(orec_mom_out, orec_mom_out + 7 * n * n_seg, 0.0);
-    if (orders && orec_n_used_out) std::fill(orec_n_used_out, orec_n_used_out + n * n_seg, (int64_t)0);
-    if (orders && tot_out) std::fill(tot_out, tot_out + prom::kOdTotals * n, 0.0);
-    return;
-  }
-  const bool want_orders = orders && (orec_mom_out || orec_n_used_out || tot_out);
-  // (before anything is launched)
-  if (orders && prom::od_workgroups(n_exp, 1, n_seg) > (((int64_t)1 << 31) - 1))
-    throw Error(PROM_E_ARG, "k_order_moments: n_exp n_seg too large for one launch");
-  if (c.highpass && prom::hp_workgroups(n, ex.hp_n_seg) > (((int64_t)1 << 31) - 1))
-    throw Error(PROM_E_ARG, "k_highpass: n_exp n_trial n_seg too large for one launch");
-  if (prom::dt_workgroups(ex.n_trial, n_pix) > (((int64_t)1 << 31) - 1))
-    throw Error(PROM_E_ARG, "k_detrend: n_trial n_pix too large for one launch");
-  const int64_t nm = n * n_pix;
-  ex.q.ensure(sizeof(double) * (size_t)n_wav);
-  try {   // the whole table's model is resident at once: it is not batched
-    ex.model.ensure(sizeof(double) * (size_t)nm);
-  } catch (const Error& err) {
-    throw Error(err.code, std::string(err.what()) + ": the recovery keeps the model of all " +
-                              std::to_string(ex.n_trial) + " trials in device memory; give fewer trials per call");
-  }
-  ex.flag.ensure((size_t)ex.n_trial * n_pix);
-  rc.W.ensure(sizeof(double) * (size_t)n_cols * n_exp * n_pix);
-  // the last calls' q, models and flags go: the aids of the expose calls have nothing to repeat
-  ex.dt_ran = ex.hp_ran = ex.od_ran = false;
-  ex.last_wav = ex.last_R = nullptr;
-  // 1: the inject call's steps; the cleaned data stay in sy.out and U in sy.U
-  sysrem_on(ctx, st, wav, R, n_wav, c, U_out, nullptr, nullptr, nullptr, false);
-  // 2: W of (U, the table's ivar)
-  prom::launch_filter_weights(st, sy.U.as<double>(), ex.ivar.as<double>(), rc.W.as<double>(), n_exp, n_cols, n_pix,
-                              nullptr, nullptr);
-  rc.last = 2;
-  rc.last_n_comp = n_cols;
-  // 3: the final model as orders_on forms it, and the moments against the cleaned data
-  const double nan = std::nan("");
-  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
-  expose_launch(ctx, st, wav, R, (int32_t)n_wav, false, ex.model.as<double>(), nullptr, nullptr);
-  if (c.highpass)
-    prom::launch_highpass(st, ex.model.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(),
-                          ex.hp_g.as<double>(), ex.hp_half, ex.hp_den, ex.hp_mode, n, ex.hp_n_seg, n_pix, nullptr,
-                          nullptr);
-  prom::launch_detrend(st, ex.model.as<double>(), sy.U.as<double>(), rc.W.as<double>(), ex.flag.as<uint8_t>(), n_exp,
-                       n_cols, ex.n_trial, n_pix, nullptr, nullptr);
-  if (mom_out || n_used_out) moments_launch(ctx, st, nullptr, nullptr, sy.out.as<double>());
-  if (want_orders) orders_launch(ctx, st, orec_mom_out, orec_n_used_out, nullptr, sy.out.as<double>());
-  if (mom_out) download(mom_out, ex.mom, 7 * n, st);
-  if (n_used_out) download(n_used_out, ex.n_used, n, st);
-  if (orders && tot_out) download(tot_out, ex.od_tot, prom::kOdTotals * n, st);
-  if (model_out) download(model_out, ex.model, nm, st);
-  PROM_HIP(hipStreamSynchronize(st));
-}
-
-}  // namespace
-
-int32_t prom_transit_recover(prom_ctx* ctx, int32_t trial, double scale, int32_t highpass, int32_t n_comp,
-                             int32_t n_iter, int32_t ones, int32_t orders, double* mom_out, int64_t* n_used_out,
-                             double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out, double* U_out,
-                             double* model_out) {
-  return guarded(ctx, [&] {
-    prom::TransitDev& tr = ctx->tr;
-    const SyCall c{2, trial, highpass, n_comp, n_iter, ones, scale};
-    recover_check(ctx, "prom_transit_recover", c, orders);
-    if (!tr.ran) throw Error(PROM_E_STATE, "prom_transit_recover: no completed run");
-    if (ctx->ex.n_orb != tr.n_orb)
-      throw Error(PROM_E_STATE, "prom_transit_recover: the exposure table has another n_orb");
-    // the last run's stream orders the recovery after it
-    recover_on(ctx, ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav, c, orders, mom_out,
-               n_used_out, orec_mom_out, orec_n_used_out, tot_out, U_out, model_out);
-  });
-}
-
-int32_t prom_spectrum_recover(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
-                              int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter,
-                              int32_t ones, int32_t orders, double* mom_out, int64_t* n_used_out,
-                              double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out, double* U_out,
-                              double* model_out) {
-  return guarded(ctx, [&] {
-    prom::SyDev& sy = ctx->sy;
-    const SyCall c{3, trial, highpass, n_comp, n_iter, ones, scale};
-    recover_check(ctx, "prom_spectrum_recover", c, orders);
-    PROM_REQUIRE(n_orb == ctx->ex.n_orb, "prom_spectrum_recover: n_orb differs from the observation's");
-    PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && wav && R, "prom_spectrum_recover: bad spectrum");
-    for (int64_t w = 0; w < n_wav; ++w)
-      PROM_REQUIRE(obs_finite(wav[w]) && (w == 0 || wav[w] >= wav[w - 1]),
-                   "prom_spectrum_recover: wavelengths must be finite and ascending");
-    const hipStream_t st = ctx->stream;
-    sy.last_source = 0;   // (the uploads may move the buffers the last call read)
-    upload(sy.wav, wav, n_wav, st);
-    upload(sy.R, R, (int64_t)n_orb * n_wav, st);
-    sy.last_n_orb = n_orb;
-    recover_on(ctx, st, sy.wav.as<double>(), sy.R.as<double>(), n_wav, c, orders, mom_out, n_used_out, orec_mom_out,
-               orec_n_used_out, tot_out, U_out, model_out);
   });
 }
 

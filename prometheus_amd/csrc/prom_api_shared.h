@@ -1,0 +1,130 @@
+// What the translation units of the C-ABI layer share (prom_api.hip, prom_api_observe.hip, prom_api_expose.hip): the
+// guard of every entry, the copies, and the few checks the observation entries make in the same words.  Host code only.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <exception>
+#include <string>
+
+#include "prom_internal.h"
+#include "vmap_index.h"
+
+namespace {
+
+using prom::DevBuf;
+using prom::Error;
+
+template <class F>
+int32_t guarded(prom_ctx* ctx, F&& f) {
+  if (!ctx) return PROM_E_ARG;
+  try {
+    PROM_HIP(hipSetDevice(ctx->device));
+    f();
+    ctx->err.clear();
+    return PROM_OK;
+  } catch (const Error& e) {
+    ctx->err = e.what();
+    return e.code;
+  } catch (const std::exception& e) {
+    ctx->err = e.what();
+    return PROM_E_HIP;
+  }
+}
+
+template <class T>
+void upload(DevBuf& b, const T* h, int64_t n, hipStream_t s) {
+  b.ensure(sizeof(T) * (size_t)std::max<int64_t>(n, 1));
+  if (n > 0) PROM_HIP(hipMemcpyAsync(b.p, h, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, s));
+}
+
+template <class T>
+void download(T* h, const DevBuf& b, int64_t n, hipStream_t s) {
+  if (n > 0) PROM_HIP(hipMemcpyAsync(h, b.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, s));
+}
+
+bool obs_finite(double v) { return std::isfinite(v); }
+
+// the spectrum the transit observe calls read: the last run's R, or its broadened R_b while that is current
+// (prom_transit_broaden)
+const double* transit_R(prom_ctx* ctx) {
+  const prom::TransitDev& tr = ctx->tr;
+  return ctx->br.current ? ctx->br.Rb.as<double>() : tr.slot[tr.last].R.as<double>();
+}
+
+// ---- the observation entries' common words ---------------------------------------------------------------------------
+// a caller's spectrum: the arrays are there (`arrays`), n_wav lies in [1, 2^30] and wav is finite and ascending
+void spectrum_check(const char* who, int64_t n_wav, const double* wav, bool arrays) {
+  const std::string w(who);
+  PROM_REQUIRE(n_wav >= 1 && n_wav <= ((int64_t)1 << 30) && arrays, w + ": bad spectrum");
+  for (int64_t i = 0; i < n_wav; ++i)
+    PROM_REQUIRE(obs_finite(wav[i]) && (i == 0 || wav[i] >= wav[i - 1]), w + ": wavelengths must be finite and ascending");
+}
+
+// a prom_spectrum_* entry's arguments: n_orb is `whose` ("the observation's"), the spectrum is sound; then drop() forgets
+// the last call (the uploads may move the buffers it read) and wav and R go to the family's buffers on the context's
+// stream, which is returned
+template <class Drop>
+hipStream_t spectrum_args(prom_ctx* ctx, const char* who, int32_t n_orb, int32_t want_n_orb, const char* whose,
+                          int64_t n_wav, const double* wav, const double* R, DevBuf& dwav, DevBuf& dR, Drop&& drop) {
+  PROM_REQUIRE(n_orb == want_n_orb, std::string(who) + ": n_orb differs from " + whose);
+  spectrum_check(who, n_wav, wav, wav && R);
+  drop();
+  upload(dwav, wav, n_wav, ctx->stream);
+  upload(dR, R, (int64_t)n_orb * n_wav, ctx->stream);
+  return ctx->stream;
+}
+
+// a prom_transit_* entry's arguments: a completed run whose n_orb is that of `what` ("the exposure table"); the last
+// run's stream orders the call after it
+struct TransitArgs {
+  hipStream_t st;
+  const double *wav, *R;
+  int64_t n_wav;
+};
+TransitArgs transit_args(prom_ctx* ctx, const char* who, int32_t n_orb, const char* what) {
+  const prom::TransitDev& tr = ctx->tr;
+  if (!tr.ran) throw Error(PROM_E_STATE, std::string(who) + ": no completed run");
+  if (n_orb != tr.n_orb) throw Error(PROM_E_STATE, std::string(who) + ": " + what + " has another n_orb");
+  return TransitArgs{ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav};
+}
+
+// "no pixel: every moment 0" for n (row, trial) pairs
+void zero_moments(int64_t n, double* mom_out, int64_t* n_used_out) {
+  if (mom_out) std::fill(mom_out, mom_out + 7 * n, 0.0);
+  if (n_used_out) std::fill(n_used_out, n_used_out + n, (int64_t)0);
+}
+
+// the batches of whole trial groups of k_vmap's partial records under the scratch cap, for a table of n_rows rows
+struct VmBatches {
+  int32_t n_chunks, n_groups, bg, nb_max;   // chunks of pixel tiles, trial groups, groups and trials of a batch at most
+};
+VmBatches vm_batches(const prom_ctx* ctx, int32_t n_rows, int32_t n_trial) {
+  VmBatches b;
+  b.n_chunks = prom::vm_chunks(ctx->obs.n_pix);
+  b.n_groups = prom::vm_groups(n_trial);
+  b.bg = prom::vm_batch_groups(ctx->vmap_scratch_bytes, n_rows, b.n_chunks, b.n_groups);
+  b.nb_max = std::min(b.bg * prom::kVmTrials, n_trial);
+  return b;
+}
+// a *_kernel_ms aid times the first batch: its time scales to the table by trial count
+double first_batch_scale(int32_t n_trial, int32_t nb_max) { return (double)n_trial / (double)nb_max; }
+
+// the loop of the *_kernel_ms aids: every stream idle, then n_runs times launch() on st and, once st is through, the
+// time between events ev[2 i] and ev[2 i + 1] of the context added to sum[i], for i < n_pairs
+template <class Launch>
+void time_launches(prom_ctx* ctx, hipStream_t st, int32_t n_runs, int n_pairs, double* sum, Launch&& launch) {
+  for (auto s : ctx->streams) PROM_HIP(hipStreamSynchronize(s));
+  std::fill(sum, sum + n_pairs, 0.0);
+  for (int32_t r = 0; r < n_runs; ++r) {
+    launch();
+    PROM_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n_pairs; ++i) {
+      float ms = 0.0f;
+      PROM_HIP(hipEventElapsedTime(&ms, ctx->ev[2 * i], ctx->ev[2 * i + 1]));
+      sum[i] += ms;
+    }
+  }
+}
+
+}  // namespace
