@@ -1,5 +1,6 @@
-// What the translation units of the C-ABI layer share (prom_api.hip, prom_api_observe.hip, prom_api_expose.hip): the
-// guard of every entry, the copies, and the few checks the observation entries make in the same words.  Host code only.
+// What the translation units of the C-ABI layer share (prom_api.hip, prom_api_transit.hip, prom_api_observe.hip,
+// prom_api_expose.hip): the guard of every entry, the copies, the checks of tables and density models, and the few
+// checks the observation entries make in the same words.  Host code only.
 #pragma once
 
 #include <algorithm>
@@ -9,6 +10,11 @@
 
 #include "prom_internal.h"
 #include "vmap_index.h"
+
+namespace prom {
+// whether [p, p + n) lies in a buffer of the pinned host pool that is in use (prom_api.hip: prom_host_alloc)
+bool pinned_holds(const void* p, size_t n);
+}  // namespace prom
 
 namespace {
 
@@ -41,6 +47,46 @@ void upload(DevBuf& b, const T* h, int64_t n, hipStream_t s) {
 template <class T>
 void download(T* h, const DevBuf& b, int64_t n, hipStream_t s) {
   if (n > 0) PROM_HIP(hipMemcpyAsync(h, b.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, s));
+}
+
+prom::DensityDev to_dev(const prom_density_model& m) {
+  prom::DensityDev d{};
+  d.kind = m.kind;
+  for (int i = 0; i < 8; ++i) d.p[i] = m.p[i];
+  // power law with a small integral exponent q (the setup files' q_esc, e.g. 6): (R / r)^q by repeated
+  // squaring on the device (pad = q + 1) instead of a general pow.  Each squaring doubles the relative error
+  // already carried, so the error grows about linearly in q: q <= 8 keeps it within ~8 ulp of pow
+  // (test_density_plugins, q = 6); larger exponents take pow
+  if (m.kind == PROM_DENSITY_POWERLAW && m.p[2] >= 0.0 && m.p[2] <= 8.0 && m.p[2] == std::floor(m.p[2]))
+    d.pad = (int32_t)m.p[2] + 1;
+  return d;
+}
+
+bool valid_kind(int32_t k) { return k >= PROM_DENSITY_BAROMETRIC && k <= PROM_DENSITY_GRIDDED; }
+
+// GRIDDED: grid sizes from p[0..2] (each >= 2) and the packed length of [gx, gy, gz, values]
+bool gridded_dims(const prom_density_model& m, int64_t* nx, int64_t* ny, int64_t* nz, int64_t* len) {
+  for (int i = 0; i < 3; ++i)
+    if (!(m.p[i] >= 2.0 && m.p[i] <= 1.0e6 && m.p[i] == std::floor(m.p[i]))) return false;
+  *nx = (int64_t)m.p[0];
+  *ny = (int64_t)m.p[1];
+  *nz = (int64_t)m.p[2];
+  *len = *nx + *ny + *nz + *nx * *ny * *nz;
+  return *nx * *ny * *nz < ((int64_t)1 << 31);
+}
+
+template <class T>
+bool table_ok(const std::vector<T>& v, int32_t id) {
+  return id >= 0 && id < (int32_t)v.size() && v[id].live;
+}
+
+// a problem's captured graphs go with its buffers and arguments (a new set, a freed table, the context's end)
+void drop_graphs(prom::TransitDev& tr) {
+  for (auto& g : tr.gexec)
+    if (g) {
+      (void)hipGraphExecDestroy(g);
+      g = nullptr;
+    }
 }
 
 bool obs_finite(double v) { return std::isfinite(v); }

@@ -153,7 +153,7 @@ __device__ __forceinline__ double interp_guess(double t, int32_t g, XF X2, RF RE
 
 __device__ __forceinline__ int32_t seg_guess(double t, double b, double inv, int32_t m) {
   // f = fma(t, inv, b) (b = -x_lo inv), g = (f < 0 ? 0 : f >= m - 2 ? m - 2 : (int)f): the host's verified
-  // map (prom_api.hip sigma segments).  Every target lies in the slice, so f is within rounding of
+  // map (prom_segments.hip build_sigma_segments).  Every target lies in the slice, so f is within rounding of
   // [0, m - 1] and truncating first, clamping the integer after, gives the same g
   const int32_t g = (int32_t)__builtin_fma(t, inv, b);
   return max(min(g, m - 2), 0);   // (one v_med3_i32; m >= 2)

@@ -150,7 +150,7 @@ __global__ void k_table_recs(const double* __restrict__ x, const double* __restr
   if (amax) amax[i] = am;
 }
 
-// prom_transit_set's small inputs arrive in one DMA (descriptors + data, prom_api.hip Stager); a workgroup
+// prom_transit_set's small inputs arrive in one DMA (descriptors + data, prom_api_transit.hip Stager); a workgroup
 // per descriptor scatters its bytes to the destination buffer (8-byte words, then the byte tail)
 __global__ void __launch_bounds__(kBlock) k_scatter(const char* __restrict__ base, const ScatterDesc* __restrict__ d) {
   const ScatterDesc e = d[blockIdx.x];

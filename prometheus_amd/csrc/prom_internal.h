@@ -1,4 +1,4 @@
-// Internal declarations shared by the C-ABI layer (prom_api.hip) and the kernels (prom_kernels.hip).
+// Internal declarations shared by the C-ABI layer (prom_api*.hip), the host planners and the kernels' translation units.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -79,7 +79,7 @@ constexpr int kWinMaxSpecies = 4;
 // (prom_kernels.hip Monos / TailDeg: degree 7 for one effective species, 3 otherwise)
 inline int n_tail_moments(int S) { return S == 1 ? 8 : (S + 1) * (S + 2) * (S + 3) / 6; }
 
-// Doppler cross-section rows: table nodes a resampling workgroup stages in LDS per species (prom_api.hip
+// Doppler cross-section rows: table nodes a resampling workgroup stages in LDS per species (prom_segments.hip
 // sigma segments; larger slices gather from the global table).
 #ifndef PROM_SIG_SEG
 #define PROM_SIG_SEG 416   // (LDS slice cap: 416 nodes keep a 3-species k_sigma_tc workgroup at 31 KB; r04o sweep)
@@ -104,7 +104,7 @@ constexpr int kSigBlockW = 256;   // wavelengths per resampling workgroup (== kB
 #endif
 constexpr int kSigRowChunk = PROM_SIG_ROWS;   // rows per resampling workgroup (4, 8 or 16)
 
-// Stellar-spectrum path: star-table nodes a tau workgroup stages in LDS (prom_api.hip rm_slices).
+// Stellar-spectrum path: star-table nodes a tau workgroup stages in LDS (prom_segments.hip star_slices).
 constexpr int kRmStarMax = 1024;
 
 // Device-side view of one density model (the prom_density_model scalars).
@@ -154,7 +154,7 @@ struct ScatterDesc {
   int64_t bytes;
 };
 
-// Per 256-wavelength block and atomic slot of a Doppler-row problem (prom_api.hip sigma segments): the
+// Per 256-wavelength block and atomic slot of a Doppler-row problem (prom_segments.hip sigma segments): the
 // table nodes [lo, lo + m) every row's targets fall between, and, for kind > 0, a linear bracket guess
 // g(t) = clamp((int)fma(t, inv, xs), 0, m - 2) (xs holds -x_lo inv) that the host verified to be within one node of numpy's
 // bracket for every target in the slice.  kind & 3: 0 no guess (general lookup); 1 the slice fits in LDS;
@@ -588,6 +588,15 @@ struct ColPlan {
   int kind;
 };
 ColPlan col_plan(const TransitDev& tr);
+// the route predicates, written once for col_plan and prom_transit_set's buffer sizes.  k_columns8 takes the problem
+// (else the generic k_ntot + k_columns: n_x > 64, > 8 terms or > 4 scenarios):
+inline bool cols8_path(const TransitDev& tr) { return tr.n_mol == 0 && tr.n_x <= 64 && tr.n_terms <= 8 && tr.n_sc <= 4; }
+// the windowed tau kernels take it:
+inline bool win_path(const TransitDev& tr) {
+  return tr.exp_mode && tr.n_mol == 0 && tr.n_atoms >= 1 && tr.n_atoms <= kWinMaxSpecies;
+}
+// the fast atomic path (sigma resampled beside k_columns8; runs pipelined):
+inline bool fast_path(const TransitDev& tr) { return cols8_path(tr) && win_path(tr) && tr.window && !tr.star; }
 // orbital Doppler shift: the per-phase cross-section rows, Y or sigma_s, and the Q ranges (prom_sigma.hip)
 void launch_sigma_rows(hipStream_t s, int32_t nsig, const SigTabs4& tabv, const double* wav, int64_t n_wav,
                        int32_t n_rows, const SigSeg* seg, const int32_t* fb, int32_t n_fb, double* sig, float4* tq,
@@ -622,6 +631,34 @@ bool build_target_windows(const double* wav, int64_t n_wav, const double* shift,
                           const std::vector<const std::vector<double>*>& tabs, int32_t lds, int32_t lamcap,
                           int32_t rowcap, int64_t pmax, std::vector<SigSeg>& seg_out, std::vector<int32_t>& row_out,
                           std::vector<int32_t>& lam_out, int32_t& n_win);
+// ---- prom_transit_set's pure host arithmetic (prom_segments.hip; tests/test_segments_cpu.py) ----
+// the range of n Doppler factors; false when one is not positive and finite
+bool factor_range(const double* v, int64_t n, double& smin, double& smax);
+// the sigma segments of the Doppler rows: seg[blocks][n_atoms]; seg4, the per-wavefront entries [blocks][n_atoms][4]
+// followed by the n_dir bucket directories' SigSeg; sdir, their buckets; the oversize blocks of kSigSeg (fb) and of
+// tc_slice_cap (fb_tc); noguess, the (block, species) pairs with neither a guess nor a directory
+struct SigmaSegments {
+  std::vector<SigSeg> seg, seg4;
+  std::vector<int32_t> sdir, fb, fb_tc;
+  int64_t n_dir = 0, noguess = 0;
+};
+// tabs, shift: per atomic slot its table's nodes (AtomTable::hx: build_directory fills it with the table's n nodes at
+// every upload, so its size is AtomTable::n) and its n_orb factors; use_dir false: no directories; no_guess:
+// every kind 0 (validation).  false: no segments for this number of slots
+bool build_sigma_segments(const double* wav, int64_t n_wav, const std::vector<const std::vector<double>*>& tabs,
+                          const std::vector<const double*>& shift, int64_t n_orb, bool use_dir, bool no_guess,
+                          SigmaSegments& out);
+// mirror[i]: the chord at (y_i, -z_i) or -1 (k_mol_list); returns the number of pairs
+int64_t pair_mirrors(const double* cy, const double* cz, int64_t n_pr, std::vector<int32_t>& mirror);
+// per 256-wavelength tile {lo, m, half} of the star table nodes its targets lambda / s reach, s in [s_min, s_max]
+// (k_tau_rm); m = 0: more than kRmStarMax nodes, or factors that are not positive and finite
+std::vector<int32_t> star_slices(const double* wav, int64_t n_wav, const std::vector<double>& X, double s_min,
+                                 double s_max);
+// polynomial sigma rows: the smallest even degree D in [4, 14] with amax^(D+1)/(D+1)! <= 2^-53 over the tables'
+// AtomTable::amax; 0 (exp10 rows) when disabled, when an amax is NaN or when none fits
+int32_t sigma_poly_degree(const double* amax, int32_t n_tables, bool enabled);
+// whether p[0] bounds a built-in density (kind, p) on its domain: the profile decays away from its body
+bool density_bounded(int32_t kind, const double* p);
 // AtomTable::rec from a table's x and y, and the per-interval |a| bounds (prom_fn.hip)
 void launch_table_recs(hipStream_t s, const double* x, const double* y, int64_t n, double4* rec, double* amax);
 void launch_scatter(hipStream_t s, const char* base, const ScatterDesc* d, int32_t n);

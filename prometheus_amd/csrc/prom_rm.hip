@@ -11,8 +11,8 @@ namespace prom {
 // per-set quantity (k_rm_fout); a run visits only the chords blocked or active at some phase of its group
 // (F once per such (chord, wavelength), shared by the group's phases) and subtracts their loss from Fout.
 // F_star(t) = 10^(f_k + slope_k (t - x_k)) is evaluated as 10^f_k * exp(ln10 slope_k (t - x_k)) on the
-// LDS copy of the star-table slice that the workgroup's targets t = lambda / s can reach (prom_api.hip
-// rm_slices), bracketed through a slice-local bucket directory; a tile whose slice exceeds kRmStarMax
+// LDS copy of the star-table slice that the workgroup's targets t = lambda / s can reach (prom_segments.hip
+// star_slices), bracketed through a slice-local bucket directory; a tile whose slice exceeds kRmStarMax
 // nodes uses the global lookup (sigma_of).  With one shift for every chord (no rotation) F_star is
 // evaluated once per wavelength.
 constexpr int kRmChunk = 64;       // chords staged in LDS per sweep

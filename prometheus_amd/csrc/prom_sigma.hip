@@ -20,7 +20,7 @@ constexpr int kSigFbRows = PROM_SIG_FB_ROWS;   // rows per gathering workgroup (
 #endif
 
 // ---- Doppler-shifted cross-section rows (orbital Doppler shift: one row per phase) ----------------
-// The host (prom_api.hip sigma segments) gives, per 256-wavelength block and atomic slot, the table nodes
+// The host (prom_segments.hip sigma segments) gives, per 256-wavelength block and atomic slot, the table nodes
 // [lo, lo + m) that every row's shifted targets shift_o * lambda_w fall between: positive factors and
 // IEEE multiplication are monotone, so fl(shift_o lambda_w) lies in [fl(s_min lambda_first),
 // fl(s_max lambda_last)].  Same bracket rule, slope, products and exp10 as sigma_of / sigma_multi: the

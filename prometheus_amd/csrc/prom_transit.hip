@@ -2221,9 +2221,9 @@ static int col_spec_kind(const TransitDev& tr, const ColArgs& cargs, int32_t n_t
 // prom_transit_set's PROM_DEBUG line
 ColPlan col_plan(const TransitDev& tr) {
   ColPlan p{};
-  p.wpath = tr.exp_mode && tr.n_mol == 0 && tr.n_atoms >= 1 && tr.n_atoms <= kWinMaxSpecies;
-  p.cols8 = tr.n_mol == 0 && tr.n_x <= 64 && tr.n_terms <= 8 && tr.n_sc <= 4;
-  p.pre_sigma = p.cols8 && p.wpath && tr.window && !tr.star;
+  p.wpath = win_path(tr);
+  p.cols8 = cols8_path(tr);
+  p.pre_sigma = fast_path(tr);
   p.msp = p.pre_sigma && tr.species_merge_ok;
   p.na = p.msp ? 1 : tr.n_atoms;
   p.n_terms = p.msp ? 1 : tr.n_terms;

@@ -3,7 +3,7 @@
 // (build_target_windows: the window's SigSeg per species and its staged wavelengths [lw0, lw1)) instead of per wave
 // from the slices.  64 bytes: one scalar load.
 //
-// Plain inline functions shared by the host (prom_api.hip: the upload), the kernel and the host harness of
+// Plain inline functions shared by the host (prom_api_transit.hip: the upload), the kernel and the host harness of
 // tests/test_tw_stage_cpu.py, as tw_index.h's.
 //
 // The pool: staged species (SigSeg kind & 1: kinds 1 and 3) lie in species order, species s at pool entries

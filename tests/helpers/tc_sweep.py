@@ -242,7 +242,7 @@ def near_boundary(q, rel=2.0 ** -40):
     return (m < 0.5 * (1 + rel)) | (m > 1 - rel)
 
 
-# ---- which k_tc_build configuration a chord count reaches (prom_api.hip, prom_transit.hip, prom_tcurve.hip) ---------
+# ---- which k_tc_build configuration a chord count reaches (prom_api_transit.hip, prom_transit.hip, prom_tcurve.hip) --
 def build_config(n_pr, parts_env=None):
     """(front end, parts, chord source) for n_pr chords: the partials of k_columns8 when n_pr % 32 == 0, else sweeps
     of 3,072 chords; (n_pr + 299) / 300 parts capped at 16 unless PROM_TC_PARTS; a part of <= 1,024 chords is staged

@@ -158,7 +158,7 @@ def inputs(name, n=None):
 
 class Caps:
     def __init__(self, n_orb, tup=(), **knobs):
-        """prom_transit_set's caps (prom_api.hip build_tw): the defaults from n_orb, or the PROM_TW_* knobs of tup
+        """prom_transit_set's caps (prom_api_transit.hip target_windows): the defaults from n_orb, or the PROM_TW_* knobs of tup
         (test_windows_small_caps_bitwise's order) or by name (ROWCAP="100")."""
         e = dict(zip(("ROWCAP", "PMAX", "LDS", "LAMCAP", "LAMFIT", "EXACT", "ALIGN", "RP"), tup), **knobs)
         self.rowcap = max(1, int(e["ROWCAP"])) if "ROWCAP" in e else max(256, min(768, (4096 // max(1, n_orb)) // 64 * 64))

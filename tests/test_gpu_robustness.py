@@ -258,7 +258,7 @@ def test_failed_set_does_not_commit_sigma_segments(dev):
     """A prom_transit_set that builds new Doppler sigma segments and then fails (here: a stellar table with
     a non-zero offset, rejected after the segments are built) must not leave its segment key behind: the
     same problem without the star rebuilds the segments instead of reusing ones that never reached the
-    device, and matches the oracle (prom_api.hip seg_key_valid)."""
+    device, and matches the oracle (prom_api_transit.hip seg_key_valid)."""
     from prometheus_amd import configs, setupfile, _native
     cfg = configs.reduced(configs.get("C4"), orbphase_steps=3, lower_w=5886e-8, upper_w=5900e-8,
                           res_low=5e-9, res_high=1e-10)

@@ -46,7 +46,7 @@ def test_design_covers_every_branch(kind):
     if kind == "two":
         # truncated at the 64-octave cap: the exact sum runs between the cap and the top
         assert sw["cap"] == 2.0 ** 57 and np.count_nonzero((q > sw["cap"]) & (q < sw["top"])) >= 16
-    # the polynomial lookups' range: ln10 |dy| <= 0.0866 keeps degree <= 14 (prom_api.hip sig_deg)
+    # the polynomial lookups' range: ln10 |dy| <= 0.0866 keeps degree <= 14 (prom_segments.hip sigma_poly_degree)
     assert np.log(10.0) * np.max(np.diff(sw["ty"])) < 0.0866
 
 

@@ -1,6 +1,6 @@
 // Host harness of the target windows' stage records, for CPU tests only (tests/test_tw_stage_cpu.py).
 //
-// Compiled as C++ with g++ against prometheus_amd/csrc/tw_stage.h, the very text prom_api.hip (the upload) and
+// Compiled as C++ with g++ against prometheus_amd/csrc/tw_stage.h, the very text prom_api_transit.hip (the upload) and
 // k_sigma_tw (the staging prologue) compile: tw_stage_records derives the records of a plan as prom_transit_set does,
 // tw_stage_entries walks every pool entry of every window the way the prologue does -- its species from the
 // record's boundaries, its table record, the LDS slots of its node x and of its {E, L} -- and tw_stage_bases
