@@ -348,7 +348,9 @@ int32_t prom_vmap_set(prom_ctx* ctx, int32_t n_orb, int32_t n_trial, const doubl
  * n_used_out [n_orb][n_trial]; either may be NULL.  The partial records of the kernel take
  * n_orb * n_trial * ceil(ceil(n_pix / 32) / 16) * 64 bytes of device scratch, capped at 256 MiB, or at
  * PROM_VMAP_SCRATCH_MB megabytes (fractions allowed) from the environment at context creation: a larger table runs in
- * batches of whole groups of 8 trials (one group at least), with the same results bit for bit. */
+ * batches of whole groups of 8 trials (one group at least), with the same results bit for bit.  (The one other cap
+ * read from the environment is PROM_GRID_SCRATCH_MB, megabytes of work buffers of an injection grid's sub-batch,
+ * default 4096, read at every grid call: "injection grids on the device" below.) */
 int32_t prom_transit_vmap(prom_ctx* ctx, double* mom_out, int64_t* n_used_out);
 /* The same for a spectrum the caller supplies: wav[n_wav] finite and ascending, R[n_orb][n_wav], n_orb the table's
  * (the checks of prom_spectrum_observe). */
@@ -824,6 +826,62 @@ int32_t prom_spectrum_recover(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const
                               int32_t ones, int32_t orders, double* mom_out, int64_t* n_used_out,
                               double* orec_mom_out, int64_t* orec_n_used_out, double* tot_out, double* U_out,
                               double* model_out);
+
+/* ---- injection grids on the device --------------------------------------------------------------
+ * A list of n_inj injections, entry b = (trial[b], scale[b]), cleaned (the inject grid calls) or cleaned and recovered
+ * (the recover grid calls) in one call: the injections of a grid are independent, so they share every launch.
+ *
+ *   equivalence          entry b of every output equals, bit for bit, NaN pattern and signs of zero included, what
+ *                        prom_spectrum_inject / prom_spectrum_recover (prom_transit_* for the transit calls) returns
+ *                        for (trial[b], scale[b]) with the same other arguments on the same context state
+ *   independence         entry b does not depend on n_inj, on b's position, on the other entries (duplicates are
+ *                        allowed) or on how the call cuts the list into sub-batches.  raw, the table's data and the
+ *                        resident filter are never written or replaced
+ *   steps                the factors of the listed trials as a table of B trials, k_expose unchanged over it,
+ *                        D[b] from raw, that model and scale[b]; the resident high-pass over the B n_exp rows; SYSREM
+ *                        with the injection as a grid dimension of every launch: 2 + n_cols + n_comp (2 n_iter + 1)
+ *                        launches per sub-batch, not per injection; a component that ends stops its own injection
+ *                        alone.  A recover grid call forms and high-passes the model of all trials once per call,
+ *                        forms W of every (U[b], ivar) in one launch, and per injection filters the model out of place
+ *                        into a second buffer and takes the moments (with orders = 1 also the totals) against
+ *                        cleaned[b]
+ *   outputs              inject grid: U_out[n_inj][n_exp][n_comp + ones], cleaned_out[n_inj][n_exp][n_pix],
+ *                        injected_out[n_inj][n_exp][n_pix].  recover grid: mom_out[n_inj][n_exp][n_trial][7],
+ *                        n_used_out[n_inj][n_exp][n_trial], tot_out[n_inj][n_exp][n_trial][4] (untouched with
+ *                        orders = 0), U_out[n_inj][n_exp][n_comp + ones].  Any of them may be NULL.  The per-order
+ *                        records and the final model are not part of the grid calls: prom_*_recover gives them for one
+ *                        point
+ *   errors               the single calls', before anything is launched; PROM_E_ARG also for n_inj < 0, a missing
+ *                        trial or scale array with n_inj > 0, a trial outside [0, n_trial) or a scale that is not
+ *                        finite (the message names the entry), and a sub-batch too large for one launch of k_highpass
+ *   empty                n_inj = 0 writes nothing and succeeds; n_pix = 0 gives per entry what the single calls give
+ *   sub-batches          per injection the work buffers take about (5 + n_cols for a recovery) n_exp n_pix 8 bytes.
+ *                        The list is cut into sub-batches of as many injections as fit PROM_GRID_SCRATCH_MB megabytes
+ *                        (fractions allowed; default 4096), one at least and 65,535 at most; the variable is read
+ *                        from the environment at every grid call.  Each sub-batch's outputs are copied to the caller's
+ *                        arrays and the stream waits before the next one reuses the buffers
+ *   memory               a recover grid call keeps the unfiltered and one filtered model of all trials, twice the
+ *                        recover call's n_exp n_trial n_pix 8 bytes: PROM_E_NOMEM with the same remedy
+ *   afterwards           the work buffers hold the last sub-batch, so prom_sysrem_kernel_ms has no call to repeat and
+ *                        fails with PROM_E_STATE, as prom_filter_kernel_ms does unless a prom_detrend_build came last;
+ *                        the aids of the expose calls have nothing to repeat after a recover grid call */
+int32_t prom_transit_inject_grid(prom_ctx* ctx, int32_t n_inj, const int32_t* trial, const double* scale,
+                                 int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out,
+                                 double* cleaned_out, double* injected_out);
+/* The same for a spectrum the caller supplies (the checks of prom_spectrum_expose). */
+int32_t prom_spectrum_inject_grid(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                  int32_t n_inj, const int32_t* trial, const double* scale, int32_t highpass,
+                                  int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out, double* cleaned_out,
+                                  double* injected_out);
+/* The recovery of every entry, on the last run's R (its broadened R_b while that is current). */
+int32_t prom_transit_recover_grid(prom_ctx* ctx, int32_t n_inj, const int32_t* trial, const double* scale,
+                                  int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones, int32_t orders,
+                                  double* mom_out, int64_t* n_used_out, double* tot_out, double* U_out);
+/* The same for a spectrum the caller supplies (the checks of prom_spectrum_expose). */
+int32_t prom_spectrum_recover_grid(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                   int32_t n_inj, const int32_t* trial, const double* scale, int32_t highpass,
+                                   int32_t n_comp, int32_t n_iter, int32_t ones, int32_t orders, double* mom_out,
+                                   int64_t* n_used_out, double* tot_out, double* U_out);
 
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop

@@ -172,6 +172,15 @@ SIGNATURES = {
     "prom_spectrum_recover": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, C.c_double, C.c_int32,
                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.POINTER(C.c_int64), _dp,
                                           C.POINTER(C.c_int64), _dp, _dp, _dp]),
+    "prom_transit_inject_grid": (C.c_int32, [C.c_void_p, C.c_int32, _ip, _dp, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, _dp, _dp, _dp]),
+    "prom_spectrum_inject_grid": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _ip, _dp,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "prom_transit_recover_grid": (C.c_int32, [C.c_void_p, C.c_int32, _ip, _dp, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, _dp, C.POINTER(C.c_int64), _dp, _dp]),
+    "prom_spectrum_recover_grid": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _ip, _dp,
+                                               C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp,
+                                               C.POINTER(C.c_int64), _dp, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -1008,6 +1017,81 @@ class Device:
         self._check(self.lib.prom_spectrum_recover(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(trial),
                                                    float(scale), int(bool(highpass)), int(n_comp), int(n_iter),
                                                    int(bool(ones)), int(bool(orders)), *ptr), "prom_spectrum_recover")
+        return out
+
+    # ---- injection grids (prom_hip.h "injection grids on the device") ---------------------------
+    @staticmethod
+    def _grid_list(trials, scales, who: str):
+        """The list of a grid call as (n_inj, int32 trials, float64 scales), one entry per injection."""
+        t = np.ascontiguousarray(trials, dtype=np.int32)
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        if t.ndim != 1 or s.shape != t.shape:
+            raise ValueError("%s: trials and scales must be two lists of one length" % who)
+        return len(t), t, s
+
+    def _inject_grid_outputs(self, n_inj: int, n_comp: int, ones: bool, data: bool, injected: bool):
+        n_exp, _, n_pix = self._ex_shape or (0, 0, 0)
+        U = np.zeros((n_inj, n_exp, max(int(n_comp) + int(bool(ones)), 0)))
+        cleaned = np.full((n_inj, n_exp, n_pix), np.nan) if data else None
+        inj = np.full((n_inj, n_exp, n_pix), np.nan) if injected else None
+        return (U, cleaned, inj), (_d(U), _d(cleaned) if data else None, _d(inj) if injected else None)
+
+    def transit_inject_grid(self, trials, scales, n_comp: int, n_iter: int = 30, ones: bool = False,
+                            highpass: bool = False, data: bool = True, injected: bool = False):
+        """prom_transit_inject_grid: every (trials[b], scales[b]) injected into the raw exposures from the last run's
+        model and cleaned, in one call: (U [n_inj][n_exp][n_comp + ones], cleaned [n_inj][n_exp][n_pix] or None
+        without ``data``, injected likewise or None), entry b what transit_inject gives for that point."""
+        n_inj, t, s = self._grid_list(trials, scales, "transit_inject_grid")
+        out, ptr = self._inject_grid_outputs(n_inj, n_comp, ones, data, injected)
+        self._check(self.lib.prom_transit_inject_grid(self.h, n_inj, t.ctypes.data_as(_ip), _d(s), int(bool(highpass)),
+                                                      int(n_comp), int(n_iter), int(bool(ones)), *ptr),
+                    "prom_transit_inject_grid")
+        return out
+
+    def spectrum_inject_grid(self, wav, R, trials, scales, n_comp: int, n_iter: int = 30, ones: bool = False,
+                             highpass: bool = False, data: bool = True, injected: bool = False):
+        """prom_spectrum_inject_grid: the same for R[n_orb][n_wav] on the ascending grid wav."""
+        wav, R = _spectrum(wav, R, "spectrum_inject_grid")
+        n_inj, t, s = self._grid_list(trials, scales, "spectrum_inject_grid")
+        out, ptr = self._inject_grid_outputs(n_inj, n_comp, ones, data, injected)
+        self._check(self.lib.prom_spectrum_inject_grid(self.h, R.shape[0], len(wav), _d(wav), _d(R), n_inj,
+                                                       t.ctypes.data_as(_ip), _d(s), int(bool(highpass)), int(n_comp),
+                                                       int(n_iter), int(bool(ones)), *ptr),
+                    "prom_spectrum_inject_grid")
+        return out
+
+    def _recover_grid_outputs(self, n_inj: int, n_comp: int, ones: bool, orders: bool, moments: bool, totals: bool):
+        n_exp, n_trial, _ = self._ex_shape or (0, 0, 0)
+        U = np.zeros((n_inj, n_exp, max(int(n_comp) + int(bool(ones)), 0)))
+        mom = np.zeros((n_inj, n_exp, n_trial, 7)) if moments else None
+        nu = np.zeros((n_inj, n_exp, n_trial), dtype=np.int64) if moments else None
+        tot = np.zeros((n_inj, n_exp, n_trial, 4)) if orders and totals else None
+        return (mom, nu, tot, U), (_d(mom) if moments else None,
+                                   nu.ctypes.data_as(C.POINTER(C.c_int64)) if moments else None,
+                                   _d(tot) if tot is not None else None, _d(U))
+
+    def transit_recover_grid(self, trials, scales, n_comp: int, n_iter: int = 30, ones: bool = False,
+                             highpass: bool = False, orders: bool = False, moments: bool = True, totals: bool = True):
+        """prom_transit_recover_grid: every (trials[b], scales[b]) injected, cleaned and recovered in one call:
+        (moments [n_inj][n_exp][n_trial][7], n_used [n_inj][n_exp][n_trial], totals [n_inj][n_exp][n_trial][4] or None
+        without ``orders``, U [n_inj][n_exp][n_comp + ones]), entry b what transit_recover gives for that point."""
+        n_inj, t, s = self._grid_list(trials, scales, "transit_recover_grid")
+        out, ptr = self._recover_grid_outputs(n_inj, n_comp, ones, orders, moments, totals)
+        self._check(self.lib.prom_transit_recover_grid(self.h, n_inj, t.ctypes.data_as(_ip), _d(s), int(bool(highpass)),
+                                                       int(n_comp), int(n_iter), int(bool(ones)), int(bool(orders)),
+                                                       *ptr), "prom_transit_recover_grid")
+        return out
+
+    def spectrum_recover_grid(self, wav, R, trials, scales, n_comp: int, n_iter: int = 30, ones: bool = False,
+                              highpass: bool = False, orders: bool = False, moments: bool = True, totals: bool = True):
+        """prom_spectrum_recover_grid: the same for R[n_orb][n_wav] on the ascending grid wav."""
+        wav, R = _spectrum(wav, R, "spectrum_recover_grid")
+        n_inj, t, s = self._grid_list(trials, scales, "spectrum_recover_grid")
+        out, ptr = self._recover_grid_outputs(n_inj, n_comp, ones, orders, moments, totals)
+        self._check(self.lib.prom_spectrum_recover_grid(self.h, R.shape[0], len(wav), _d(wav), _d(R), n_inj,
+                                                        t.ctypes.data_as(_ip), _d(s), int(bool(highpass)), int(n_comp),
+                                                        int(n_iter), int(bool(ones)), int(bool(orders)), *ptr),
+                    "prom_spectrum_recover_grid")
         return out
 
     # ---- stellar disk -----------------------------------------------------------------------

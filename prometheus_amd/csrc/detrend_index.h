@@ -91,14 +91,21 @@ PROM_OBS_HD bool dt_coefficients(const double* M, int64_t m_stride, const double
 
 // Apply: M'_e = M_e, then in ascending k M'_e = fl(M'_e - fl(U[e][k] c_k)), written over M_e; NaN down a column
 // that is not filterable.
+// The out-of-place form reads the column of S and writes the column of M (the same strides): the same values in the
+// same order, so M's bits are the in-place form's whatever S is, M itself included.
 template <int NC>
-PROM_OBS_HD void dt_apply(double* M, int64_t m_stride, const double* U, int32_t n_exp, const double (&c)[NC], bool ok) {
+PROM_OBS_HD void dt_apply(const double* S, double* M, int64_t m_stride, const double* U, int32_t n_exp,
+                          const double (&c)[NC], bool ok) {
   for (int32_t e = 0; e < n_exp; ++e) {
-    double m = M[e * m_stride];
+    double m = S[e * m_stride];
 #pragma unroll
     for (int k = 0; k < NC; ++k) m = dt_add(m, -dt_mul(U[dt_u(e, k, NC)], c[k]));
     M[e * m_stride] = ok ? m : __builtin_nan("");
   }
+}
+template <int NC>
+PROM_OBS_HD void dt_apply(double* M, int64_t m_stride, const double* U, int32_t n_exp, const double (&c)[NC], bool ok) {
+  dt_apply<NC>(M, M, m_stride, U, n_exp, c, ok);
 }
 
 }  // namespace prom

@@ -12,6 +12,7 @@
 #include "order_index.h"
 #include "sysrem_index.h"
 #include "filter_index.h"
+#include "grid_index.h"
 
 namespace {
 
@@ -187,9 +188,11 @@ ChainCall resident_call(prom_ctx* ctx, bool highpass, bool detrend, bool orders,
 }
 
 // the moments of the model in ex.model against `data`, in batches of whole trial groups (ev: events around the first
-// batch's k_model_moments)
-void moments_launch(prom_ctx* ctx, hipStream_t st, const double* data, hipEvent_t ev0, hipEvent_t ev1) {
+// batch's k_model_moments; model: another buffer of ex.model's shape, a recovery grid's)
+void moments_launch(prom_ctx* ctx, hipStream_t st, const double* data, hipEvent_t ev0, hipEvent_t ev1,
+                    const double* model = nullptr) {
   prom::ExDev& ex = ctx->ex;
+  if (!model) model = ex.model.as<double>();
   const prom::ObsDev& ob = ctx->obs;
   const VmBatches b = vm_batches(ctx, ex.n_exp, ex.n_trial);
   ex.part.ensure(sizeof(double) * (size_t)prom::vm_part_doubles(ex.n_exp, b.nb_max, b.n_chunks));
@@ -199,7 +202,7 @@ void moments_launch(prom_ctx* ctx, hipStream_t st, const double* data, hipEvent_
                  ex.n_trial, b.n_groups, (b.n_groups + b.bg - 1) / b.bg, b.bg, b.n_chunks);
   for (int32_t g = 0; g < b.n_groups; g += b.bg) {
     const int32_t j_first = prom::vm_group_first(g), nb = std::min(b.nb_max, ex.n_trial - j_first);
-    prom::launch_model_moments(st, ex.model.as<double>(), ex.flag.as<uint8_t>(), data, ex.ivar.as<double>(), ob.n_pix,
+    prom::launch_model_moments(st, model, ex.flag.as<uint8_t>(), data, ex.ivar.as<double>(), ob.n_pix,
                                ex.n_exp, ex.n_trial, j_first, nb, ex.part.as<double>(), g == 0 ? ev0 : nullptr,
                                g == 0 ? ev1 : nullptr);
     prom::launch_vmap_reduce(st, ex.part.as<double>(), ob.n_pix, ex.n_exp, ex.n_trial, j_first, nb, ex.mom.as<double>(),
@@ -222,10 +225,11 @@ OdBatches od_batches(const prom_ctx* ctx) {
 
 // k_order_moments + k_order_totals over the final model in ex.model against `data`, in batches of whole trial groups
 // under the scratch cap (one group at least); a batch's records go to the caller's arrays when they are wanted (ev:
-// events around the two kernels of the first batch)
+// events around the two kernels of the first batch; model: as moments_launch's)
 void orders_launch(prom_ctx* ctx, hipStream_t st, const double* data, double* orec_mom_out, int64_t* orec_n_used_out,
-                   hipEvent_t* ev) {
+                   hipEvent_t* ev, const double* model = nullptr) {
   prom::ExDev& ex = ctx->ex;
+  if (!model) model = ex.model.as<double>();
   const int32_t n_pix = ctx->obs.n_pix, n_seg = ex.od_n_seg;
   const OdBatches b = od_batches(ctx);
   ex.od_rec.ensure(sizeof(double) * (size_t)prom::od_record_doubles(ex.n_exp, b.nb_max, n_seg));
@@ -239,7 +243,7 @@ void orders_launch(prom_ctx* ctx, hipStream_t st, const double* data, double* or
   if (want) host.resize((size_t)prom::od_record_doubles(ex.n_exp, b.nb_max, n_seg));
   for (int32_t g = 0; g < b.n_groups; g += b.bg) {
     const int32_t j_first = prom::od_group_first(g), nb = std::min(b.nb_max, ex.n_trial - j_first);
-    prom::launch_order_moments(st, ex.model.as<double>(), ex.flag.as<uint8_t>(), data, ex.ivar.as<double>(),
+    prom::launch_order_moments(st, model, ex.flag.as<uint8_t>(), data, ex.ivar.as<double>(),
                                ex.od_seg.as<int32_t>(), ex.od_perm.as<int32_t>(), n_pix, ex.n_exp, ex.n_trial, j_first,
                                nb, n_seg, ex.od_rec.as<double>(), ev && g == 0 ? ev[0] : nullptr,
                                ev && g == 0 ? ev[1] : nullptr);
@@ -965,6 +969,270 @@ int32_t prom_spectrum_recover(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const
     const hipStream_t st = sy_spectrum(ctx, "prom_spectrum_recover", n_orb, n_wav, wav, R);
     recover_on(ctx, st, sy.wav.as<double>(), sy.R.as<double>(), n_wav, c, orders,
                ExOut{mom_out, n_used_out, orec_mom_out, orec_n_used_out, tot_out, model_out}, U_out);
+  });
+}
+
+// ------------------------------------------------------------------------------ injection grids
+namespace {
+
+// a list of injections: entry b is (trial[b], scale[b])
+struct GridList {
+  int32_t n_inj;
+  const int32_t* trial;
+  const double* scale;
+};
+
+// the cap on the work buffers of a sub-batch, read at every grid call
+int64_t grid_cap_bytes() {
+  double mb = 4096.0;
+  if (const char* e = std::getenv("PROM_GRID_SCRATCH_MB")) {
+    const double v = std::atof(e);
+    if (v > 0.0 && v < 1.0e7) mb = v;
+  }
+  return std::max<int64_t>(1, (int64_t)(mb * 1048576.0));
+}
+
+// the refusals of the list, after the single calls' own (c holds a trial and a scale that pass them)
+void grid_check(prom_ctx* ctx, const char* who, const GridList& g) {
+  const std::string w(who);
+  if (g.n_inj < 0) throw Error(PROM_E_ARG, w + ": n_inj must be >= 0");
+  if (g.n_inj > 0 && (!g.trial || !g.scale)) throw Error(PROM_E_ARG, w + ": trial and scale missing");
+  for (int32_t b = 0; b < g.n_inj; ++b) {
+    if (g.trial[b] < 0 || g.trial[b] >= ctx->ex.n_trial)
+      throw Error(PROM_E_ARG, w + ": trial outside [0, n_trial) in entry " + std::to_string(b));
+    if (!std::isfinite(g.scale[b])) throw Error(PROM_E_ARG, w + ": scale must be finite in entry " + std::to_string(b));
+  }
+}
+
+// injections of a sub-batch under the cap, and the launches of a sub-batch that grow with it, before anything runs
+int32_t grid_plan(prom_ctx* ctx, const SyCall& c, int32_t n_inj, bool recover) {
+  const prom::ExDev& ex = ctx->ex;
+  const int64_t per = prom::gr_injection_bytes(ex.n_exp, ctx->obs.n_pix, c.n_comp + c.ones, ex.n_tap, recover);
+  const int32_t nb = prom::gr_sub_batch(grid_cap_bytes(), per, n_inj);
+  if (c.highpass && prom::hp_workgroups((int64_t)nb * ex.n_exp, ex.hp_n_seg) > kMaxGrid)
+    throw Error(PROM_E_ARG, "k_highpass: n_inj n_exp n_seg too large for one launch");
+  static const bool debug = std::getenv("PROM_DEBUG") != nullptr;
+  if (debug)
+    std::fprintf(stderr, "prom: injection grid: %d injections in %d sub-batches of up to %d, %lld bytes each\n", n_inj,
+                 prom::gr_sub_batches(n_inj, nb), nb, (long long)per);
+  return nb;
+}
+
+// the work buffers of sub-batches of up to nb injections, and the list on the device
+void grid_buffers(prom_ctx* ctx, hipStream_t st, const SyCall& c, const GridList& g, int32_t nb, int64_t n_wav,
+                  bool recover) {
+  prom::SyDev& sy = ctx->sy;
+  const prom::ExDev& ex = ctx->ex;
+  const int32_t n_exp = sy.n_exp, n_pix = sy.n_pix, n_cols = c.n_comp + c.ones;
+  const size_t B = (size_t)nb, n = (size_t)n_exp * n_pix, work = (size_t)(n_exp * prom::sy_pitch(n_pix));
+  sy.D.ensure(sizeof(double) * B * n);
+  sy.out.ensure(sizeof(double) * B * n);
+  sy.r.ensure(sizeof(double) * B * work);
+  sy.w.ensure(sizeof(double) * B * work);
+  sy.a.ensure(sizeof(double) * B * n_exp);
+  sy.ended.ensure(sizeof(int32_t) * B * prom::kGrFlags);
+  sy.part.ensure(2 * sizeof(double) * B * n_exp * prom::sy_tiles(n_pix));
+  sy.U.ensure(sizeof(double) * B * n_exp * n_cols);
+  sy.q.ensure(sizeof(double) * (size_t)n_wav);
+  sy.Fj.ensure(sizeof(double) * B * n_exp * ex.n_tap);
+  sy.model.ensure(sizeof(double) * B * n);
+  sy.epart.ensure(sizeof(double) *
+                  (size_t)prom::vm_part_doubles(n_exp, vm_batches(ctx, n_exp, nb).nb_max, prom::vm_chunks(n_pix)));
+  if (recover) ctx->rc.W.ensure(sizeof(double) * B * n_cols * n);
+  upload(sy.trial, g.trial, g.n_inj, st);
+  upload(sy.scale, g.scale, g.n_inj, st);
+}
+
+// the inject call's steps for the injections [b0, b0 + nb) of the list, nothing waits: D (injected, high-passed),
+// out (cleaned) and U of the sub-batch stay in sy.D, sy.out and sy.U as [nb][...]
+void grid_clean(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, const SyCall& c,
+                int32_t b0, int32_t nb) {
+  prom::SyDev& sy = ctx->sy;
+  prom::ExDev& ex = ctx->ex;
+  const prom::ObsDev& ob = ctx->obs;
+  const int32_t n_exp = sy.n_exp, n_pix = sy.n_pix;
+  // the models of the listed trials: their factors as a table of nb trials, through k_expose unchanged
+  prom::launch_gather_grid(st, ex.F.as<double>(), sy.Fj.as<double>(), sy.trial.as<int32_t>() + b0, n_exp, ex.n_trial,
+                           ex.n_tap, nb);
+  const VmBatches vb = vm_batches(ctx, n_exp, nb);
+  for (int32_t g = 0; g < vb.n_groups; g += vb.bg) {
+    const int32_t j_first = prom::vm_group_first(g), nj = std::min(vb.nb_max, nb - j_first);
+    prom::launch_expose(st, wav, sy.q.as<double>(), R, (int32_t)n_wav, ob.lam.as<double>(), ob.sig.as<double>(), ob.k,
+                        ex.row.as<int32_t>(), ex.a.as<double>(), sy.Fj.as<double>(), ex.data.as<double>(),
+                        ex.ivar.as<double>(), n_pix, n_exp, nb, ex.n_tap, j_first, nj, sy.epart.as<double>(),
+                        sy.model.as<double>(), nullptr, nullptr);
+  }
+  prom::launch_inject_grid(st, sy.raw.as<double>(), sy.model.as<double>(), sy.scale.as<double>() + b0,
+                           sy.D.as<double>(), n_exp, n_pix, nb);
+  if (c.highpass)
+    prom::launch_highpass(st, sy.D.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(), ex.hp_g.as<double>(),
+                          ex.hp_half, ex.hp_den, ex.hp_mode, (int64_t)nb * n_exp, ex.hp_n_seg, n_pix, nullptr, nullptr);
+  prom::launch_sysrem(st, sy.D.as<double>(), ex.ivar.as<double>(), sy.r.as<double>(), sy.w.as<double>(),
+                      sy.a.as<double>(), sy.ended.as<int32_t>(), sy.part.as<double>(), sy.U.as<double>(),
+                      sy.out.as<double>(), n_exp, n_pix, c.n_comp, c.n_iter, c.ones, nb);
+}
+
+// no pixel: every component of every entry ends at once
+void grid_zero_U(const SyCall& c, int32_t n_exp, int32_t n_inj, double* U_out) {
+  const int32_t n_cols = c.n_comp + c.ones;
+  if (!U_out) return;
+  for (int64_t i = 0; i < (int64_t)n_inj * n_exp; ++i)
+    for (int32_t k = 0; k < n_cols; ++k) U_out[i * n_cols + k] = (c.ones && k == 0) ? 1.0 : 0.0;
+}
+
+// what a grid call leaves: the work buffers hold a sub-batch, so prom_sysrem_kernel_ms has no call to repeat, nor has
+// prom_filter_kernel_ms after a recover call
+void grid_forget(prom_ctx* ctx) {
+  ctx->sy.last_source = 0;
+  if (ctx->rc.last == 2) ctx->rc.last = 0;
+}
+
+// the shared tail of the two inject grid calls on stream st
+void inject_grid_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, const SyCall& c,
+                    const GridList& g, double* U_out, double* cleaned_out, double* injected_out) {
+  prom::SyDev& sy = ctx->sy;
+  const int32_t n_exp = sy.n_exp, n_pix = sy.n_pix, n_cols = c.n_comp + c.ones;
+  const int64_t n = (int64_t)n_exp * n_pix, nu = (int64_t)n_exp * n_cols;
+  if (n_pix == 0) return grid_zero_U(c, n_exp, g.n_inj, U_out);
+  if (g.n_inj == 0 || (!U_out && !cleaned_out && !injected_out)) return;
+  const int32_t nb_max = grid_plan(ctx, c, g.n_inj, false);
+  grid_forget(ctx);
+  grid_buffers(ctx, st, c, g, nb_max, n_wav, false);
+  const double nan = std::nan("");
+  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, sy.q.as<double>());
+  for (int32_t s = 0; s < prom::gr_sub_batches(g.n_inj, nb_max); ++s) {
+    const int32_t b0 = prom::gr_sub_first(s, nb_max), nb = prom::gr_sub_count(s, nb_max, g.n_inj);
+    grid_clean(ctx, st, wav, R, n_wav, c, b0, nb);
+    if (U_out) download(U_out + b0 * nu, sy.U, nb * nu, st);
+    if (cleaned_out) download(cleaned_out + b0 * n, sy.out, nb * n, st);
+    if (injected_out) download(injected_out + b0 * n, sy.D, nb * n, st);
+    PROM_HIP(hipStreamSynchronize(st));   // (the next sub-batch writes the same buffers; the last: the end of the call)
+  }
+}
+
+// the shared tail of the two recover grid calls on stream st: the final model of every trial before the filter once
+// (k_expose, k_highpass) into ex.model, which then stays; per sub-batch the inject grid's steps and W of every (U[b],
+// ivar); per injection the filter out of place into rc.model and the moments against cleaned[b]
+void recover_grid_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R, int64_t n_wav, const SyCall& c,
+                     int32_t orders, const GridList& g, double* mom_out, int64_t* n_used_out, double* tot_out,
+                     double* U_out) {
+  prom::ExDev& ex = ctx->ex;
+  prom::SyDev& sy = ctx->sy;
+  prom::RcDev& rc = ctx->rc;
+  const int32_t n_pix = ctx->obs.n_pix, n_exp = ex.n_exp, n_cols = c.n_comp + c.ones;
+  const int64_t nu = (int64_t)n_exp * n_cols, nm = (int64_t)n_exp * ex.n_trial;
+  if (!orders) tot_out = nullptr;
+  if (n_pix == 0) {   // no pixel: zeros, and the inject call's U
+    zero_moments(g.n_inj * nm, mom_out, n_used_out);
+    if (tot_out) std::fill(tot_out, tot_out + prom::kOdTotals * g.n_inj * nm, 0.0);
+    return grid_zero_U(c, n_exp, g.n_inj, U_out);
+  }
+  if (g.n_inj == 0) return;
+  const ChainCall cc{c.highpass != 0, true, orders != 0, &sy.U, &rc.W, n_cols, &sy.out, Ran::none, true,
+                     "the recovery keeps", ExOut{}};
+  const int32_t nb_max = grid_plan(ctx, c, g.n_inj, true);
+  chain_prepare(ctx, cc, n_wav);
+  try {   // the filtered model of one injection beside the unfiltered one
+    rc.model.ensure(sizeof(double) * (size_t)(nm * n_pix));
+  } catch (const Error& err) {
+    throw Error(err.code, std::string(err.what()) + ": the recovery grid keeps a second model of all " +
+                              std::to_string(ex.n_trial) + " trials in device memory; give fewer trials per call");
+  }
+  record_last(ex, nullptr, nullptr, 0, Ran::none, 0);
+  grid_forget(ctx);
+  grid_buffers(ctx, st, c, g, nb_max, n_wav, true);
+  const double nan = std::nan("");
+  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, sy.q.as<double>());
+  prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
+  expose_launch(ctx, st, wav, R, (int32_t)n_wav, false, ex.model.as<double>(), nullptr, nullptr);
+  if (c.highpass)
+    prom::launch_highpass(st, ex.model.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(),
+                          ex.hp_g.as<double>(), ex.hp_half, ex.hp_den, ex.hp_mode, nm, ex.hp_n_seg, n_pix, nullptr,
+                          nullptr);
+  for (int32_t s = 0; s < prom::gr_sub_batches(g.n_inj, nb_max); ++s) {
+    const int32_t b0 = prom::gr_sub_first(s, nb_max), nb = prom::gr_sub_count(s, nb_max, g.n_inj);
+    grid_clean(ctx, st, wav, R, n_wav, c, b0, nb);
+    if (U_out) download(U_out + b0 * nu, sy.U, nb * nu, st);
+    prom::launch_filter_weights(st, sy.U.as<double>(), ex.ivar.as<double>(), rc.W.as<double>(), n_exp, n_cols, n_pix,
+                                nullptr, nullptr, nb);
+    for (int32_t b = 0; b < nb; ++b) {
+      const double* cleaned = sy.out.as<double>() + prom::gr_data(b, n_exp, n_pix);
+      prom::launch_detrend(st, rc.model.as<double>(), sy.U.as<double>() + prom::gr_u(b, n_exp, n_cols),
+                           rc.W.as<double>() + prom::gr_w(b, n_cols, n_exp, n_pix), ex.flag.as<uint8_t>(), n_exp, n_cols,
+                           ex.n_trial, n_pix, nullptr, nullptr, ex.model.as<double>());
+      if (mom_out || n_used_out) moments_launch(ctx, st, cleaned, nullptr, nullptr, rc.model.as<double>());
+      if (mom_out) download(mom_out + 7 * nm * (b0 + b), ex.mom, 7 * nm, st);
+      if (n_used_out) download(n_used_out + nm * (b0 + b), ex.n_used, nm, st);
+      if (tot_out) {
+        orders_launch(ctx, st, cleaned, nullptr, nullptr, nullptr, rc.model.as<double>());
+        download(tot_out + prom::kOdTotals * nm * (b0 + b), ex.od_tot, prom::kOdTotals * nm, st);
+      }
+    }
+    PROM_HIP(hipStreamSynchronize(st));   // (the next sub-batch writes the same buffers; the last: the end of the call)
+  }
+}
+
+// a SyCall whose trial and scale pass the single calls' checks: the list has its own
+SyCall grid_call(int32_t source, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones) {
+  return SyCall{source, 0, highpass, n_comp, n_iter, ones, 0.0};
+}
+
+}  // namespace
+
+int32_t prom_transit_inject_grid(prom_ctx* ctx, int32_t n_inj, const int32_t* trial, const double* scale,
+                                 int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out,
+                                 double* cleaned_out, double* injected_out) {
+  return guarded(ctx, [&] {
+    const SyCall c = grid_call(2, highpass, n_comp, n_iter, ones);
+    const GridList g{n_inj, trial, scale};
+    sysrem_check(ctx, "prom_transit_inject_grid", c);
+    grid_check(ctx, "prom_transit_inject_grid", g);
+    const TransitArgs t = ex_transit(ctx, "prom_transit_inject_grid");
+    inject_grid_on(ctx, t.st, t.wav, t.R, t.n_wav, c, g, U_out, cleaned_out, injected_out);
+  });
+}
+
+int32_t prom_spectrum_inject_grid(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                  int32_t n_inj, const int32_t* trial, const double* scale, int32_t highpass,
+                                  int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out, double* cleaned_out,
+                                  double* injected_out) {
+  return guarded(ctx, [&] {
+    prom::SyDev& sy = ctx->sy;
+    const SyCall c = grid_call(3, highpass, n_comp, n_iter, ones);
+    const GridList g{n_inj, trial, scale};
+    sysrem_check(ctx, "prom_spectrum_inject_grid", c);
+    grid_check(ctx, "prom_spectrum_inject_grid", g);
+    const hipStream_t st = sy_spectrum(ctx, "prom_spectrum_inject_grid", n_orb, n_wav, wav, R);
+    inject_grid_on(ctx, st, sy.wav.as<double>(), sy.R.as<double>(), n_wav, c, g, U_out, cleaned_out, injected_out);
+  });
+}
+
+int32_t prom_transit_recover_grid(prom_ctx* ctx, int32_t n_inj, const int32_t* trial, const double* scale,
+                                  int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones, int32_t orders,
+                                  double* mom_out, int64_t* n_used_out, double* tot_out, double* U_out) {
+  return guarded(ctx, [&] {
+    const SyCall c = grid_call(2, highpass, n_comp, n_iter, ones);
+    const GridList g{n_inj, trial, scale};
+    recover_check(ctx, "prom_transit_recover_grid", c, orders);
+    grid_check(ctx, "prom_transit_recover_grid", g);
+    const TransitArgs t = ex_transit(ctx, "prom_transit_recover_grid");
+    recover_grid_on(ctx, t.st, t.wav, t.R, t.n_wav, c, orders, g, mom_out, n_used_out, tot_out, U_out);
+  });
+}
+
+int32_t prom_spectrum_recover_grid(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                   int32_t n_inj, const int32_t* trial, const double* scale, int32_t highpass,
+                                   int32_t n_comp, int32_t n_iter, int32_t ones, int32_t orders, double* mom_out,
+                                   int64_t* n_used_out, double* tot_out, double* U_out) {
+  return guarded(ctx, [&] {
+    prom::SyDev& sy = ctx->sy;
+    const SyCall c = grid_call(3, highpass, n_comp, n_iter, ones);
+    const GridList g{n_inj, trial, scale};
+    recover_check(ctx, "prom_spectrum_recover_grid", c, orders);
+    grid_check(ctx, "prom_spectrum_recover_grid", g);
+    const hipStream_t st = sy_spectrum(ctx, "prom_spectrum_recover_grid", n_orb, n_wav, wav, R);
+    recover_grid_on(ctx, st, sy.wav.as<double>(), sy.R.as<double>(), n_wav, c, orders, g, mom_out, n_used_out, tot_out,
+                    U_out);
   });
 }
 

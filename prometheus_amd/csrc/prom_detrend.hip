@@ -11,7 +11,9 @@
 // of kDtTrials consecutive trials, so a wave reads and writes along p.  Pass 1 walks the exposures and keeps the
 // n_comp coefficients in registers (the kernel is compiled once per n_comp: no indexed register array, no scratch);
 // pass 2 walks them again and writes M' over M.  Only the column's thread touches the column, so the pass needs no
-// barrier and no second buffer.  The trials of a workgroup read the same W[k][e][p0 .. p0 + 63] lines at the same
+// barrier and no second buffer.  The out-of-place form (OUT, the recovery grids) reads the column from `src`, another
+// buffer of the same shape that stays untouched, and writes it to `model`: the same thread, the same values in the same
+// order, so the bits are the in-place form's, whose instantiation is what it was.  The trials of a workgroup read the same W[k][e][p0 .. p0 + 63] lines at the same
 // step: they share them through the compute unit's L1 (and the workgroups of other trial groups through L2), not
 // through LDS.  U[e][k] is uniform over the workgroup: scalar loads.  There is no cross-lane arithmetic, so the
 // bits do not depend on the layout.
@@ -28,19 +30,21 @@ namespace prom {
 static_assert(kDtBlock == 256 && kDtTile == 64, "a wave of k_detrend reads 64 consecutive pixels of one trial");
 static_assert(kVmTile == 32 && kVmTile * kVmTrials == kVmBlock, "one thread per (pixel, trial) of a tile");
 
-template <int NC>
-__global__ void __launch_bounds__(kDtBlock) k_detrend(double* __restrict__ model, const double* __restrict__ U,
-                                                       const double* __restrict__ W, uint8_t* __restrict__ flag,
-                                                       int32_t n_exp, int32_t n_trial, int32_t n_pix, int32_t n_tiles) {
+template <int NC, bool OUT>
+__global__ void __launch_bounds__(kDtBlock) k_detrend(double* __restrict__ model, const double* __restrict__ src,
+                                                       const double* __restrict__ U, const double* __restrict__ W,
+                                                       uint8_t* __restrict__ flag, int32_t n_exp, int32_t n_trial,
+                                                       int32_t n_pix, int32_t n_tiles) {
   const int32_t tid = threadIdx.x;
   const int32_t p = dt_pixel(dt_wg_tile(blockIdx.x, n_tiles), tid);
   const int32_t j = dt_trial(dt_wg_group(blockIdx.x, n_tiles), tid);
   if (p >= n_pix || j >= n_trial) return;
   double* M = model + ex_model(0, j, p, n_trial, n_pix);
+  const double* S = OUT ? src + ex_model(0, j, p, n_trial, n_pix) : M;   // (in place: src is not looked at)
   const int64_t m_stride = (int64_t)n_trial * n_pix;
   double c[NC];
-  const bool ok = dt_coefficients<NC>(M, m_stride, W + dt_w(0, 0, p, n_exp, n_pix), n_pix, n_exp, c);
-  dt_apply<NC>(M, m_stride, U, n_exp, c, ok);
+  const bool ok = dt_coefficients<NC>(S, m_stride, W + dt_w(0, 0, p, n_exp, n_pix), n_pix, n_exp, c);
+  dt_apply<NC>(S, M, m_stride, U, n_exp, c, ok);
   flag[dt_flag(j, p, n_pix)] = ok ? 1 : 0;
 }
 
@@ -108,7 +112,7 @@ __global__ void __launch_bounds__(kVmBlock) k_model_moments(const double* __rest
 }
 
 void launch_detrend(hipStream_t s, double* model, const double* U, const double* W, uint8_t* flag, int32_t n_exp,
-                    int32_t n_comp, int32_t n_trial, int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1) {
+                    int32_t n_comp, int32_t n_trial, int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1, const double* src) {
   if (n_pix <= 0 || n_exp <= 0 || n_trial <= 0) return;
   if (n_comp < 1 || n_comp > kDtMaxComp) throw Error(PROM_E_ARG, "k_detrend: n_comp outside [1, 16]");
   const int64_t wgs = dt_workgroups(n_trial, n_pix);
@@ -119,8 +123,12 @@ void launch_detrend(hipStream_t s, double* model, const double* U, const double*
   switch (n_comp) {
 #define PROM_DT_CASE(NC)                                                                                        \
   case NC:                                                                                                      \
-    hipLaunchKernelGGL((k_detrend<NC>), grid, dim3(kDtBlock), 0, s, model, U, W, flag, n_exp, n_trial, n_pix,   \
-                       n_tiles);                                                                                \
+    if (src && src != model)                                                                                    \
+      hipLaunchKernelGGL((k_detrend<NC, true>), grid, dim3(kDtBlock), 0, s, model, src, U, W, flag, n_exp,      \
+                         n_trial, n_pix, n_tiles);                                                              \
+    else                                                                                                        \
+      hipLaunchKernelGGL((k_detrend<NC, false>), grid, dim3(kDtBlock), 0, s, model, nullptr, U, W, flag, n_exp, \
+                         n_trial, n_pix, n_tiles);                                                              \
     break;
     PROM_DT_CASE(1) PROM_DT_CASE(2) PROM_DT_CASE(3) PROM_DT_CASE(4) PROM_DT_CASE(5) PROM_DT_CASE(6) PROM_DT_CASE(7)
     PROM_DT_CASE(8) PROM_DT_CASE(9) PROM_DT_CASE(10) PROM_DT_CASE(11) PROM_DT_CASE(12) PROM_DT_CASE(13)

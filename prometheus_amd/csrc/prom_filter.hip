@@ -12,9 +12,12 @@
 // wave: scalar loads.  Pass 1 walks the exposures and forms N, the factorisation runs in place,
 // pass 2 solves every weighted exposure without storing (an x that is not finite zeroes the whole pixel, and a W
 // entry is to be written once), pass 3 solves again and stores.  There is no cross-lane arithmetic, no atomic, no
-// barrier and no hand-off between workgroups, so a pixel's bits depend on its own column alone.
+// barrier and no hand-off between workgroups, so a pixel's bits depend on its own column alone.  blockIdx.y is the
+// injection of a recovery grid: U[b] is read and W[b] written (grid_index.h), ivar is shared; every other call is the
+// batch of one.
 #include "prom_internal.h"
 #include "filter_index.h"
+#include "grid_index.h"
 
 namespace prom {
 
@@ -33,6 +36,9 @@ __global__ void __launch_bounds__(kFwTile) k_filter_weights(const double* __rest
   if (p >= n_pix) return;
   constexpr int NR = fw_reg_entries(K), NM = fw_entries(K) - NR;
   __shared__ double lds[NM > 0 ? NM * kFwTile : 1];
+  const int32_t b = blockIdx.y;
+  U += gr_u(b, n_exp, K);
+  W += gr_w(b, K, n_exp, n_pix);
   FwTri<NR> L;
   L.mem = lds + threadIdx.x;
   L.pitch = kFwTile;
@@ -40,10 +46,11 @@ __global__ void __launch_bounds__(kFwTile) k_filter_weights(const double* __rest
 }
 
 void launch_filter_weights(hipStream_t s, const double* U, const double* ivar, double* W, int32_t n_exp, int32_t n_comp,
-                           int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1) {
-  if (n_pix <= 0 || n_exp <= 0) return;
+                           int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1, int32_t n_inj) {
+  if (n_pix <= 0 || n_exp <= 0 || n_inj <= 0) return;
+  if (n_inj > kGrMaxBatch) throw Error(PROM_E_ARG, "k_filter_weights: more than 65535 injections in one launch");
   if (n_comp < 1 || n_comp > kDtMaxComp) throw Error(PROM_E_ARG, "k_filter_weights: n_comp outside [1, 16]");
-  const dim3 grid((uint32_t)fw_tiles(n_pix));
+  const dim3 grid((uint32_t)fw_tiles(n_pix), (uint32_t)n_inj);
   if (ev0) PROM_HIP(hipEventRecord(ev0, s));
   switch (n_comp) {
 #define PROM_FW_CASE(K)                                                                                  \

@@ -506,6 +506,8 @@ struct SyDev {
   DevBuf D, out;                          // [n_exp][n_pix]: injected (and high-passed) data, cleaned data
   DevBuf r, w;                            // [n_exp][sy_pitch(n_pix)]: residuals and weights
   DevBuf a, ended, part, U;               // [n_exp], int32 [kSyMaxComp + 1], [n_exp][tiles] {num, den}, [n_exp][cols]
+  DevBuf trial, scale;                    // an injection grid's list (int32, double); its sub-batches keep [B][...] of
+                                          // D .. U above and Fj [n_exp][B][n_tap], model [n_exp][B][n_pix]
   DevBuf Fj, model, q, epart;             // one trial: factors [n_exp][n_tap], model [n_exp][n_pix], q [n_wav], k_expose's records
   DevBuf wav, R;                          // prom_spectrum_inject's copies of the caller's spectrum
   // the last call, for prom_sysrem_kernel_ms to repeat (source 0: none yet, 1: clean, 2: transit, 3: spectrum)
@@ -518,7 +520,8 @@ struct SyDev {
 // The filter's weights on the device: the recovery's own W (prom_*_recover; the resident filter of prom_detrend_set
 // lies in ExDev) and what the last k_filter_weights launch read and wrote, for prom_filter_kernel_ms to repeat.
 struct RcDev {
-  DevBuf W;                               // [n_comp + ones][n_exp][n_pix]
+  DevBuf W;                               // [n_comp + ones][n_exp][n_pix] ([B][...] in a recovery grid's sub-batch)
+  DevBuf model;                           // a recovery grid's filtered model of one injection, [n_exp][n_trial][n_pix]
   DevBuf fU, fivar, fW;                   // prom_filter_weights' copies of the caller's arrays and its W
   int32_t last = 0;                       // 0: none, 1: prom_detrend_build (ExDev's U, W), 2: a recover call (SyDev's U, W)
   int32_t last_n_comp = 0;
@@ -691,7 +694,8 @@ void launch_expose(hipStream_t s, const double* wav, const double* q, const doub
 // W[n_comp][n_exp][n_pix], flag[n_trial][n_pix] = the column is filterable; then the moments of trials
 // [j_first, j_first + nb) of that model into the batch's partial records, as launch_expose's
 void launch_detrend(hipStream_t s, double* model, const double* U, const double* W, uint8_t* flag, int32_t n_exp,
-                    int32_t n_comp, int32_t n_trial, int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1);
+                    int32_t n_comp, int32_t n_trial, int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1,
+                    const double* src = nullptr);   // (src: out of place, the model is read from src and src stays)
 void launch_model_moments(hipStream_t s, const double* model, const uint8_t* flag, const double* data,
                           const double* ivar, int32_t n_pix, int32_t n_exp, int32_t n_trial, int32_t j_first,
                           int32_t nb, double* part, hipEvent_t ev0, hipEvent_t ev1);
@@ -722,10 +726,18 @@ void launch_sysrem_gather(hipStream_t s, const double* F, double* Fj, int32_t n_
 void launch_inject(hipStream_t s, const double* raw, const double* model, double scale, double* D, int64_t n);
 void launch_sysrem(hipStream_t s, const double* D, const double* ivar, double* r, double* w, double* a, int32_t* ended,
                    double* part, double* U, double* out, int32_t n_exp, int32_t n_pix, int32_t n_comp, int32_t n_iter,
-                   int32_t ones);
+                   int32_t ones, int32_t n_inj = 1);
+// the injection grids (prom_sysrem.hip, grid_index.h): launch_sysrem with n_inj injections works on [n_inj][...] of
+// every buffer but ivar (ended: int32 [n_inj][kGrFlags]) in the same number of launches; before it the factors of the
+// listed trials as a table of n_inj trials, Fj[n_exp][n_inj][n_tap], and D[n_inj][n_exp][n_pix] from raw, the model
+// [n_exp][n_inj][n_pix] of that table and scale[n_inj] (trial and scale on the device)
+void launch_gather_grid(hipStream_t s, const double* F, double* Fj, const int32_t* trial, int32_t n_exp, int32_t n_trial,
+                        int32_t n_tap, int32_t n_inj);
+void launch_inject_grid(hipStream_t s, const double* raw, const double* model, const double* scale, double* D,
+                        int32_t n_exp, int32_t n_pix, int32_t n_inj);
 // the filter's weights (prom_filter.hip): W[n_comp][n_exp][n_pix] of U[n_exp][n_comp] and ivar[n_exp][n_pix]
 void launch_filter_weights(hipStream_t s, const double* U, const double* ivar, double* W, int32_t n_exp, int32_t n_comp,
-                           int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1);
+                           int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1, int32_t n_inj = 1);   // (U, W: [n_inj][...])
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

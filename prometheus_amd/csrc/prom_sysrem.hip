@@ -20,8 +20,16 @@
 // 64 kSyVec consecutive doubles of a row); the second walk finds most of the tile in the caches.  a[e] and the flag
 // are uniform over the workgroup.  The only cross-lane arithmetic is the butterfly of the row sums, whose shape
 // sysrem_index.h fixes as a function of n_pix alone.  No atomics, no LDS in the step, plain vector stores.
+//
+// The injection grids (prom_*_inject_grid / prom_*_recover_grid) run the same five SYSREM kernels: blockIdx.y is the
+// injection b, every per-injection buffer is [B][the single call's], and a kernel moves its pointers to b's slice
+// (grid_index.h) before it does what it did; the single call is the batch of one.  A component that ends sets flag
+// `col` of b's own row of `ended`, so it stops b's later launches and nobody else's.  Two kernels are the grid's own:
+//   k_gather_grid    Fj[e][b][tap] = F[e][trial[b]][tap]: k_expose then runs unchanged with B in n_trial's place
+//   k_inject_grid    D[b][e][p] from raw[e][p], model[e][b][p] and scale[b]
 #include "prom_internal.h"
 #include "sysrem_index.h"
+#include "grid_index.h"
 
 namespace prom {
 
@@ -48,11 +56,37 @@ __global__ void __launch_bounds__(kSyFlatBlock) k_inject(const double* __restric
   D[i] = sy_inject(raw[i], model[i], scale);
 }
 
+__global__ void __launch_bounds__(kSyFlatBlock) k_gather_grid(const double* __restrict__ F, double* __restrict__ Fj,
+                                                              const int32_t* __restrict__ trial, int32_t n_exp,
+                                                              int32_t n_trial, int32_t n_tap, int32_t n_inj) {
+  const int64_t i = (int64_t)blockIdx.x * kSyFlatBlock + threadIdx.x;
+  if (i >= (int64_t)n_exp * n_tap) return;
+  const int32_t b = blockIdx.y;
+  const int32_t e = (int32_t)(i / n_tap), tap = (int32_t)(i % n_tap);
+  Fj[gr_gather_to(e, b, tap, n_inj, n_tap)] = F[gr_gather_from(e, trial[b], tap, n_trial, n_tap)];
+}
+
+__global__ void __launch_bounds__(kSyFlatBlock) k_inject_grid(const double* __restrict__ raw,
+                                                              const double* __restrict__ model,
+                                                              const double* __restrict__ scale, double* __restrict__ D,
+                                                              int32_t n_exp, int32_t n_pix, int32_t n_inj) {
+  const int64_t i = (int64_t)blockIdx.x * kSyFlatBlock + threadIdx.x;
+  if (i >= (int64_t)n_exp * n_pix) return;
+  const int32_t b = blockIdx.y;
+  const int32_t e = (int32_t)(i / n_pix), p = (int32_t)(i % n_pix);
+  D[gr_inject_to(b, e, p, n_exp, n_pix)] =
+      sy_inject(raw[ex_data(e, p, n_pix)], model[gr_inject_model(e, b, p, n_inj, n_pix)], scale[b]);
+}
+
 __global__ void __launch_bounds__(kSyFlatBlock) k_sysrem_prep(const double* __restrict__ D, const double* __restrict__ ivar,
                                                               double* __restrict__ r, double* __restrict__ w,
                                                               int32_t n_exp, int32_t n_pix, int64_t pitch) {
   const int64_t i = (int64_t)blockIdx.x * kSyFlatBlock + threadIdx.x;
   if (i >= (int64_t)n_exp * pitch) return;
+  const int32_t b = blockIdx.y;   // the injection: its D, r and w (ivar is shared)
+  D += gr_data(b, n_exp, n_pix);
+  r += gr_work(b, n_exp, pitch);
+  w += gr_work(b, n_exp, pitch);
   const int32_t e = (int32_t)(i / pitch), p = (int32_t)(i % pitch);
   double wv = 0.0, rv = 0.0;
   if (p < n_pix) {
@@ -68,8 +102,9 @@ __global__ void __launch_bounds__(kSyFlatBlock) k_sysrem_fill(double* __restrict
                                                               int32_t col, int32_t n_cols, double value) {
   const int32_t e = blockIdx.x * kSyFlatBlock + threadIdx.x;
   if (e >= n_exp) return;
-  a[e] = value;
-  U[sy_u(e, col, n_cols)] = value;
+  const int32_t b = blockIdx.y;
+  a[gr_a(b, n_exp) + e] = value;
+  U[gr_u(b, n_exp, n_cols) + sy_u(e, col, n_cols)] = value;
 }
 
 constexpr int kSyRowsAhead = 4;   // exposures of the second walk in flight at once
@@ -111,7 +146,12 @@ __global__ void __launch_bounds__(kSyBlock) k_sysrem_step(double* __restrict__ r
                                                           const double* __restrict__ a,
                                                           const int32_t* __restrict__ ended, double2* __restrict__ part,
                                                           int32_t n_exp, int64_t pitch, int32_t n_tiles) {
-  if (*ended) return;   // (uniform: the component's norm was not > 0)
+  const int32_t b = blockIdx.y;   // the injection: its flag, r, w, a and partials
+  if (ended[gr_flag(b, 0)]) return;   // (uniform: the component's norm was not > 0)
+  r += gr_work(b, n_exp, pitch);
+  w += gr_work(b, n_exp, pitch);
+  a += gr_a(b, n_exp);
+  part += gr_part(b, n_exp, n_tiles);
   const int32_t lane = threadIdx.x, tile = blockIdx.x;
   const int32_t p = sy_pixel(tile, lane);
   // c = fit_c(a) of this lane's pixels, in ascending e
@@ -154,7 +194,12 @@ __global__ void __launch_bounds__(kSyRowsBlock) k_sysrem_rows(const double2* __r
                                                               int32_t n_cols) {
   __shared__ double sA[kSyMaxExp];
   __shared__ double sNorm;
+  const int32_t b = blockIdx.x;   // the injection: one workgroup each; its flag, partials, a and U
+  ended += gr_flag(b, 0);
   if (*ended) return;   // (every thread reads the flag before the first barrier; thread 0 sets it after the last)
+  part += gr_part(b, n_exp, n_tiles);
+  a += gr_a(b, n_exp);
+  U += gr_u(b, n_exp, n_cols);
   const int32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int32_t e = wave; e < n_exp; e += kSyRowsBlock / 64) {
     double tn = 0.0, td = 0.0;
@@ -193,6 +238,11 @@ __global__ void __launch_bounds__(kSyFlatBlock) k_sysrem_finish(const double* __
                                                                 int32_t n_exp, int32_t n_pix, int64_t pitch) {
   const int64_t i = (int64_t)blockIdx.x * kSyFlatBlock + threadIdx.x;
   if (i >= (int64_t)n_exp * n_pix) return;
+  const int32_t b = blockIdx.y;
+  D += gr_data(b, n_exp, n_pix);
+  out += gr_data(b, n_exp, n_pix);
+  r += gr_work(b, n_exp, pitch);
+  w += gr_work(b, n_exp, pitch);
   const int32_t e = (int32_t)(i / n_pix), p = (int32_t)(i % n_pix);
   const int64_t at = sy_at(e, p, pitch);
   out[ex_data(e, p, n_pix)] = w[at] > 0.0 ? r[at] : D[ex_data(e, p, n_pix)];
@@ -218,18 +268,36 @@ void launch_inject(hipStream_t s, const double* raw, const double* model, double
   PROM_HIP(hipGetLastError());
 }
 
+void launch_gather_grid(hipStream_t s, const double* F, double* Fj, const int32_t* trial, int32_t n_exp, int32_t n_trial,
+                        int32_t n_tap, int32_t n_inj) {
+  if (n_exp <= 0 || n_tap <= 0 || n_inj <= 0) return;
+  hipLaunchKernelGGL(k_gather_grid, dim3(flat_grid((int64_t)n_exp * n_tap, "k_gather_grid"), (uint32_t)n_inj),
+                     dim3(kSyFlatBlock), 0, s, F, Fj, trial, n_exp, n_trial, n_tap, n_inj);
+  PROM_HIP(hipGetLastError());
+}
+
+void launch_inject_grid(hipStream_t s, const double* raw, const double* model, const double* scale, double* D,
+                        int32_t n_exp, int32_t n_pix, int32_t n_inj) {
+  if (n_exp <= 0 || n_pix <= 0 || n_inj <= 0) return;
+  hipLaunchKernelGGL(k_inject_grid, dim3(flat_grid((int64_t)n_exp * n_pix, "k_inject_grid"), (uint32_t)n_inj),
+                     dim3(kSyFlatBlock), 0, s, raw, model, scale, D, n_exp, n_pix, n_inj);
+  PROM_HIP(hipGetLastError());
+}
+
 void launch_sysrem(hipStream_t s, const double* D, const double* ivar, double* r, double* w, double* a, int32_t* ended,
                    double* part, double* U, double* out, int32_t n_exp, int32_t n_pix, int32_t n_comp, int32_t n_iter,
-                   int32_t ones) {
-  if (n_pix <= 0 || n_exp <= 0) return;
+                   int32_t ones, int32_t n_inj) {
+  if (n_pix <= 0 || n_exp <= 0 || n_inj <= 0) return;
   if (n_exp > kSyMaxExp) throw Error(PROM_E_ARG, "k_sysrem_rows: n_exp above 4096");
+  if (n_inj > kGrMaxBatch) throw Error(PROM_E_ARG, "k_sysrem_step: more than 65535 injections in one launch");
   const int32_t n_cols = n_comp + ones, n_tiles = sy_tiles(n_pix);
   const int64_t pitch = sy_pitch(n_pix);
-  const dim3 fill_grid((uint32_t)sy_flat_workgroups(n_exp)), tiles((uint32_t)n_tiles);
+  const uint32_t B = (uint32_t)n_inj;   // the injection is blockIdx.y (blockIdx.x of the one-workgroup k_sysrem_rows)
+  const dim3 fill_grid((uint32_t)sy_flat_workgroups(n_exp), B), tiles((uint32_t)n_tiles, B);
   double2* pt = reinterpret_cast<double2*>(part);
-  PROM_HIP(hipMemsetAsync(ended, 0, sizeof(int32_t) * (kSyMaxComp + 1), s));
-  hipLaunchKernelGGL(k_sysrem_prep, dim3(flat_grid((int64_t)n_exp * pitch, "k_sysrem_prep")), dim3(kSyFlatBlock), 0, s, D,
-                     ivar, r, w, n_exp, n_pix, pitch);
+  PROM_HIP(hipMemsetAsync(ended, 0, sizeof(int32_t) * kGrFlags * (size_t)n_inj, s));
+  hipLaunchKernelGGL(k_sysrem_prep, dim3(flat_grid((int64_t)n_exp * pitch, "k_sysrem_prep"), B), dim3(kSyFlatBlock), 0,
+                     s, D, ivar, r, w, n_exp, n_pix, pitch);
   int32_t col = 0;
   if (ones) {
     hipLaunchKernelGGL(k_sysrem_fill, fill_grid, dim3(kSyFlatBlock), 0, s, a, U, n_exp, col, n_cols, 1.0);
@@ -242,14 +310,14 @@ void launch_sysrem(hipStream_t s, const double* D, const double* ivar, double* r
     for (int32_t it = 0; it < n_iter; ++it) {
       hipLaunchKernelGGL((k_sysrem_step<false>), tiles, dim3(kSyBlock), 0, s, r, w, a, ended + col, pt, n_exp, pitch,
                          n_tiles);
-      hipLaunchKernelGGL(k_sysrem_rows, dim3(1), dim3(kSyRowsBlock), 0, s, pt, a, U, ended + col, n_exp, n_tiles, col,
+      hipLaunchKernelGGL(k_sysrem_rows, dim3(B), dim3(kSyRowsBlock), 0, s, pt, a, U, ended + col, n_exp, n_tiles, col,
                          n_cols);
     }
     hipLaunchKernelGGL((k_sysrem_step<true>), tiles, dim3(kSyBlock), 0, s, r, w, a, ended + col, pt, n_exp, pitch,
                        n_tiles);
   }
-  hipLaunchKernelGGL(k_sysrem_finish, dim3(flat_grid((int64_t)n_exp * n_pix, "k_sysrem_finish")), dim3(kSyFlatBlock), 0,
-                     s, D, r, w, out, n_exp, n_pix, pitch);
+  hipLaunchKernelGGL(k_sysrem_finish, dim3(flat_grid((int64_t)n_exp * n_pix, "k_sysrem_finish"), B),
+                     dim3(kSyFlatBlock), 0, s, D, r, w, out, n_exp, n_pix, pitch);
   PROM_HIP(hipGetLastError());
 }
 

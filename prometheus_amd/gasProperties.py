@@ -801,6 +801,44 @@ class _RecoverJob:
         self.out = part
 
 
+class _InjectGridJob(_InjectJob):
+    """One Transit.inject_grid call: what _InjectJob uploads, then every injection of the list in one call."""
+
+    def __init__(self, inj, n_orb, trials, scales, n_comp, n_iter, ones, highpass=None, broaden=None, want_data=True):
+        super().__init__(inj, n_orb, 0, 0.0, n_comp, n_iter, ones, highpass, broaden)
+        self.args = dict(n_comp=n_comp, n_iter=n_iter, ones=ones, highpass=highpass is not None, data=want_data)
+        self.trials, self.scales = trials, scales
+
+    def run(self, dev, wavelength, a: int, b: int):
+        if not self.whole:   # (inject_grid refuses such a run before it starts)
+            raise RuntimeError("inject_grid: the run was split into wavelength shards or chunks")
+        if self.br is not None:
+            dev.transit_broaden()
+        return dev.transit_inject_grid(self.trials, self.scales, **self.args)
+
+    def result(self):
+        from . import observation as obs
+        ins = self.inj.exposures.instrument
+        return obs.CleanedGrid(self.trials, self.scales, self.U, None if self.data is None else ins.unsort(self.data))
+
+
+class _RecoverGridJob(_RecoverJob):
+    """One Transit.recover_grid call: what _RecoverJob uploads, then every injection of the list in one call."""
+
+    def __init__(self, inj, n_orb, trials, scales, n_comp, n_iter, ones, highpass=None, broaden=None, orders=None):
+        super().__init__(inj, n_orb, 0, 0.0, n_comp, n_iter, ones, highpass, broaden, orders)
+        self.args = dict(n_comp=n_comp, n_iter=n_iter, ones=ones, highpass=highpass is not None,
+                         orders=orders is not None)
+        self.trials, self.scales = trials, scales
+
+    def run(self, dev, wavelength, a: int, b: int):
+        if not self.whole:   # (recover_grid refuses such a run before it starts)
+            raise RuntimeError("recover_grid: the run was split into wavelength shards or chunks")
+        if self.br is not None:
+            dev.transit_broaden()
+        return dev.transit_recover_grid(self.trials, self.scales, **self.args)
+
+
 class _BroadenedJob:
     """One Transit.broadened call inside _integrate: the kernel goes to the device once while its content key is
     unchanged, then R_b of the (one) chunk's R comes back."""
@@ -1323,6 +1361,70 @@ class Transit:
             vm.order_totals = obs.OrderTotals(tot)
         vm.U = U
         return vm
+
+    def _grid_checks(self, who, inj, trials, scales, n_comp, n_iter, ones, highpass, broaden, orders, devices,
+                     max_memory_gb):
+        """The refusals of inject_grid / recover_grid, all before a device is touched: (trials, scales, n_comp, n_iter,
+        ones, n_orb, devices, max_memory_gb) as the jobs take them."""
+        from . import observation as obs
+        n_comp, n_iter, ones = obs._check_sysrem_args(who, inj, n_comp, n_iter, ones, highpass)
+        if broaden is not None and not isinstance(broaden, obs.Broadening):
+            raise TypeError("%s: broaden must be an observation.Broadening" % who)
+        if orders is not None:
+            if not isinstance(orders, obs.Orders):
+                raise TypeError("%s: orders must be an observation.Orders" % who)
+            if orders.exposures_key != inj.exposures_key:
+                raise ValueError("%s: the Orders were made for other exposures (another table, pixels or data)" % who)
+        trials, scales = obs._check_grid_list(who, inj, trials, scales)
+        exposures = inj.exposures
+        n_orb = len(self.spatialGrid.constructOrbphaseAxis())
+        if int(exposures.rows.max()) >= n_orb or int(exposures.rows.min()) < 0:
+            raise ValueError("%s: a tap reads row %d, the transit has %d phases"
+                             % (who, int(exposures.rows.max()), n_orb))
+        if not hasattr(self, "wavelength"):
+            self.addWavelength()
+        devices = [0] if devices is None else list(devices)
+        max_memory_gb = 2.0 if max_memory_gb is None else max_memory_gb
+        n_wav, chunk = len(self.wavelength), self._wavelength_chunk(max_memory_gb, n_orb)
+        if len(devices) != 1 or n_wav > chunk:
+            raise ValueError(
+                "%s: the run would be split into %d wavelength shard(s) and chunks of %d wavelengths (the grid "
+                "has %d); a tap's model M = num / den needs the sums of the whole grid.  Give one device and raise "
+                "max_memory_gb until the grid fits one chunk." % (who, len(devices), chunk, n_wav))
+        return trials, scales, n_comp, n_iter, ones, n_orb, devices, max_memory_gb
+
+    def inject_grid(self, inj, trials, scales, n_comp: int = 6, n_iter: int = 30, ones: bool = False, highpass=None,
+                    broaden=None, data: bool = True, devices: Optional[Sequence[int]] = None,
+                    max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0):
+        """A grid of injections cleaned in one call on the device: entry b is what Transit.inject returns for
+        (trials[b], scales[b]) with the same other arguments, bit for bit (include/prom_hip.h, "injection grids on
+        the device"); the injections share every kernel launch.  ``trials`` and ``scales`` are two lists of one
+        length (a scalar is broadcast; observation.injection_grid gives a cross product).  Returns an
+        observation.CleanedGrid; with ``data=False`` only the bases U come back.  One device and one chunk, as for
+        inject.  TypeError / ValueError for bad arguments, before a device is touched."""
+        trials, scales, n_comp, n_iter, ones, n_orb, devices, max_memory_gb = self._grid_checks(
+            "inject_grid", inj, trials, scales, n_comp, n_iter, ones, highpass, broaden, None, devices, max_memory_gb)
+        job = _InjectGridJob(inj, n_orb, trials, scales, n_comp, n_iter, ones, highpass, broaden, bool(data))
+        self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
+        return job.result()
+
+    def recover_grid(self, inj, trials, scales, n_comp: int = 6, n_iter: int = 30, ones: bool = False, highpass=None,
+                     orders=None, broaden=None, devices: Optional[Sequence[int]] = None,
+                     max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0):
+        """A grid of injections cleaned and recovered in one call on the device: entry b is what Transit.recover
+        returns for (trials[b], scales[b]) with the same other arguments, bit for bit, without the per-order records
+        and the model.  The model of all trials is formed and high-passed once for the whole grid; per injection only
+        the filter and the moments run.  Returns an observation.RecoveryGrid (``order_totals`` when ``orders`` are
+        given).  One device and one chunk, as for recover.  TypeError / ValueError for bad arguments, before a device
+        is touched."""
+        from . import observation as obs
+        trials, scales, n_comp, n_iter, ones, n_orb, devices, max_memory_gb = self._grid_checks(
+            "recover_grid", inj, trials, scales, n_comp, n_iter, ones, highpass, broaden, orders, devices,
+            max_memory_gb)
+        job = _RecoverGridJob(inj, n_orb, trials, scales, n_comp, n_iter, ones, highpass, broaden, orders)
+        self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
+        mom, nu, tot, U = job.out
+        return obs.RecoveryGrid(trials, scales, mom, nu, U, inj.exposures.factors, tot)
 
     def filter_weights(self, exposures, U, devices: Optional[Sequence[int]] = None) -> np.ndarray:
         """W[n_comp][n_exp][n_pix] of the basis ``U`` [n_exp][n_comp] under the inverse variances of ``exposures``, as

@@ -485,6 +485,91 @@ class Cleaned:
         self.U, self.data, self.injected = U, data, injected
 
 
+class CleanedGrid:
+    """What Transit.inject_grid returns: ``trials`` and ``scales`` [n_inj], ``U`` [n_inj][n_exp][n_comp + ones] and
+    ``data`` [n_inj][n_exp][n_pix] in the caller's pixel order (None when the data were not asked for).  ``grid[b]`` is
+    the Cleaned that Transit.inject returns for (trials[b], scales[b])."""
+
+    def __init__(self, trials, scales, U, data=None):
+        self.trials, self.scales, self.U, self.data = trials, scales, U, data
+
+    def __len__(self):
+        return len(self.trials)
+
+    def __getitem__(self, b):
+        b = range(len(self))[b]
+        return Cleaned(self.U[b], None if self.data is None else self.data[b])
+
+
+class RecoveryGrid:
+    """What Transit.recover_grid returns: ``trials`` and ``scales`` [n_inj], ``moments`` [n_inj][n_exp][n_trial][7],
+    ``n_used`` [n_inj][n_exp][n_trial], ``U`` [n_inj][n_exp][n_comp + ones], the exposures' ``factors`` and, when
+    orders were given, ``order_totals``: one OrderTotals per injection (None otherwise).  ``grid[b]`` is the
+    VelocityMap that Transit.recover returns for (trials[b], scales[b]), without a model and per-order records."""
+
+    def __init__(self, trials, scales, moments, n_used, U, factors, order_totals=None):
+        self.trials, self.scales, self.moments, self.n_used, self.U = trials, scales, moments, n_used, U
+        self.factors = factors
+        self.order_totals = None if order_totals is None else [OrderTotals(t) for t in order_totals]
+
+    def __len__(self):
+        return len(self.trials)
+
+    def __getitem__(self, b):
+        b = range(len(self))[b]
+        vm = VelocityMap(self.moments[b], self.n_used[b], self.factors)
+        if self.order_totals is not None:
+            vm.by_order = None
+            vm.order_totals = self.order_totals[b]
+        vm.U = self.U[b]
+        return vm
+
+    def total(self, stat="chi2"):
+        """The statistic (a name of VelocityMap's) summed over the exposures, per injection: [n_inj][n_trial]."""
+        return np.array([self[b].total(stat) for b in range(len(self))]).reshape(len(self), self.moments.shape[2])
+
+
+def injection_grid(trials, scales):
+    """The cross product of ``trials`` and ``scales`` as the two flat lists of Transit.inject_grid / recover_grid,
+    trial-major: entry i * len(scales) + k is (trials[i], scales[k])."""
+    t = np.asarray(trials)
+    s = np.asarray(scales, dtype=np.float64)
+    if t.ndim != 1 or s.ndim != 1:
+        raise ValueError("injection_grid: trials and scales must be one-dimensional")
+    if t.dtype.kind not in "iu" and t.size:
+        raise TypeError("injection_grid: trials must be integers")
+    return np.repeat(t.astype(np.int64), len(s)), np.tile(s, len(t))
+
+
+def _check_grid_list(who, inj, trials, scales):
+    """The list of Transit.inject_grid / recover_grid as (int64 trials, float64 scales) of one length; a scalar is
+    broadcast against the other.  TypeError / ValueError as Transit.inject's for a single point."""
+    try:
+        t = np.atleast_1d(np.asarray(trials))
+        s = np.atleast_1d(np.asarray(scales, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise TypeError("%s: trials must be integers and scales numbers" % who) from None
+    if t.dtype.kind not in "iu" and t.size:
+        raise TypeError("%s: trials must be integers" % who)
+    if t.ndim != 1 or s.ndim != 1:
+        raise ValueError("%s: trials and scales must be scalars or one-dimensional" % who)
+    if len(t) != len(s):
+        if np.ndim(trials) == 0:
+            t = np.repeat(t, len(s))
+        elif np.ndim(scales) == 0:
+            s = np.repeat(s, len(t))
+        else:
+            raise ValueError("%s: %d trials and %d scales" % (who, len(t), len(s)))
+    t = t.astype(np.int64)
+    n_trial = inj.exposures.n_trial
+    for b in range(len(t)):
+        if not 0 <= t[b] < n_trial:
+            raise ValueError("%s: trial %d of entry %d lies outside [0, %d)" % (who, t[b], b, n_trial))
+        if not np.isfinite(s[b]):
+            raise ValueError("%s: scale of entry %d must be finite" % (who, b))
+    return t, s
+
+
 def _check_sysrem_args(who, inj, n_comp, n_iter, ones, highpass):
     """The refusals of Transit.clean / Transit.inject that need no device: (n_comp, n_iter, ones) as integers."""
     if not isinstance(inj, Injection):
