@@ -544,6 +544,35 @@ int32_t prom_spectrum_expose_highpass(prom_ctx* ctx, int32_t n_orb, int64_t n_wa
  * each repetition forms the unfiltered model again (untimed) before it.  PROM_E_STATE when there is no such call. */
 int32_t prom_highpass_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out);
 
+/* ---- median high-pass on the device ---------------------------------------------------------------
+ * Many pipelines remove the continuum with a running median along each order, because a median does not chase deep
+ * lines or cosmic-ray residue.  The resident high-pass is of one of two kinds: the weighted mean above, or the running
+ * median defined here.  Whichever was set last runs wherever "the resident high-pass" runs: prom_*_expose_highpass,
+ * prom_*_expose_orders, prom_sysrem_clean, prom_*_inject, prom_*_recover, prom_*_inject_grid, prom_*_recover_grid.
+ * Everything above stands with B defined as follows.  All float64.
+ *
+ *   window               the segments seg_first[n_seg + 1] / perm[n_pix] are the mean's, the half width 0 <= h <= 512,
+ *                        the mode 0 (subtract) or 1 (divide).  At position i of a segment of length n the window holds
+ *                        the values M_i' for i' in [max(0, i - h), min(n - 1, i + h)] that are not NaN: clipped at the
+ *                        segment's ends as the mean's is, nothing is reflected.  c is their count
+ *   order of the values  the c values sorted ascending in the IEEE order of non-NaN doubles with -0 below +0 and the
+ *                        infinities as ordinary values: the order of the bit patterns under the usual order-preserving
+ *                        integer key (negative: all bits flipped, otherwise: the sign bit set).  This fixes the bits
+ *                        among ties, of which only the sign of zero can be seen
+ *   running median       c odd: B_i is the value at index (c - 1) / 2.  c even: B_i = fl(fl(lo + hi) 0.5) with lo and hi
+ *                        at the indices c / 2 - 1 and c / 2
+ *   filtered model       M'_i = fl(M_i - B_i) or fl(M_i / B_i).  M'_i is NaN exactly where M_i is: a valid M_i has
+ *                        c >= 1, so B exists.  What IEEE gives otherwise stands (inf - inf, +inf + -inf, 0 / 0)
+ *   degenerate cases     h = 0 or n = 1: B = M
+ * B is a selection, so the bits do not depend on how a kernel finds it.  numpy's nanmedian of each window equals B
+ * under ==; the integer key adds the sign of zero.
+ *
+ * Make the median resident in the place of any high-pass set before: the checks, PROM_E_ARG / PROM_E_STATE rules and
+ * lifetime of prom_highpass_set, without taps.  prom_highpass_set puts the mean back.  prom_highpass_kernel_ms times
+ * whichever kind is resident (k_median or k_highpass). */
+int32_t prom_highpass_set_median(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32_t* seg_first,
+                                 const int32_t* perm, int32_t half_width, int32_t mode);
+
 /* ---- per-order moments on the device ------------------------------------------------------------
  * The likelihood of high-resolution data is defined per spectrum, that is per (exposure, echelle order): each order
  * has its own N, its own variances of data and model and its own best-fit scale, and orders are weighted or dropped

@@ -140,6 +140,8 @@ SIGNATURES = {
     "prom_detrend_kernel_ms": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
     "prom_highpass_set": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.c_int32, _dp, C.c_int32]),
+    "prom_highpass_set_median": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32), C.c_int32, C.c_int32]),
     "prom_transit_expose_highpass": (C.c_int32, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_int64), _dp]),
     "prom_spectrum_expose_highpass": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _dp,
                                                   C.POINTER(C.c_int64), _dp]),
@@ -754,6 +756,21 @@ class Device:
                     "prom_highpass_set")
         self._hp_key = key
 
+    def highpass_set_median(self, seg_first, perm, half_width: int, mode: int = 0, key=None) -> None:
+        """prom_highpass_set_median: a running median over half_width (0 .. 512) positions either side as the high-pass
+        of the resident exposure table, in the place of any set before; the segments, mode and ``key`` as for
+        highpass_set."""
+        seg = np.ascontiguousarray(seg_first, dtype=np.int32)
+        pm = np.ascontiguousarray(perm, dtype=np.int32)
+        if seg.ndim != 1 or len(seg) < 2 or pm.ndim != 1:
+            raise ValueError("highpass_set_median: seg_first must be [n_seg + 1] and perm [n_pix]")
+        self._hp_key = None
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.prom_highpass_set_median(self.h, len(pm), len(seg) - 1, seg.ctypes.data_as(ip),
+                                                      pm.ctypes.data_as(ip), int(half_width), int(mode)),
+                    "prom_highpass_set_median")
+        self._hp_key = key
+
     @property
     def highpass_key(self):
         """The ``key`` of the high-pass resident on the context (None: none, or set without a key)."""
@@ -776,8 +793,8 @@ class Device:
         return out
 
     def highpass_kernel_ms(self, n_runs: int = 20) -> float:
-        """prom_highpass_kernel_ms: mean device duration [ms] of k_highpass over the whole table for the last
-        high-pass call."""
+        """prom_highpass_kernel_ms: mean device duration [ms] of k_highpass (k_median when a median is resident) over
+        the whole table for the last high-pass call."""
         ms = C.c_double(0.0)
         self._check(self.lib.prom_highpass_kernel_ms(self.h, int(n_runs), C.byref(ms)), "prom_highpass_kernel_ms")
         return float(ms.value)

@@ -102,6 +102,18 @@ void zero_outputs(const prom::ExDev& ex, const ExOut& o) {
   if (o.tot) std::fill(o.tot, o.tot + prom::kOdTotals * n, 0.0);
 }
 
+// the resident high-pass, whichever kind it is (the weighted mean of prom_highpass_set or the median of
+// prom_highpass_set_median), over n_rows rows of `model` in place
+void highpass_launch(const prom::ExDev& ex, hipStream_t st, double* model, int64_t n_rows, int32_t n_pix,
+                     hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+  if (ex.hp_kind == 1)
+    prom::launch_median(st, model, ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(), ex.hp_half, ex.hp_mode, n_rows,
+                        ex.hp_n_seg, n_pix, ev0, ev1);
+  else
+    prom::launch_highpass(st, model, ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(), ex.hp_g.as<double>(),
+                          ex.hp_half, ex.hp_den, ex.hp_mode, n_rows, ex.hp_n_seg, n_pix, ev0, ev1);
+}
+
 // which *_kernel_ms aid may repeat the call that ends
 enum class Ran { none, detrend, highpass, orders };
 
@@ -302,9 +314,8 @@ void chain_model(prom_ctx* ctx, hipStream_t st, const ChainCall& c, const double
   const int32_t n_pix = ctx->obs.n_pix;
   expose_launch(ctx, st, wav, R, n_wav, false, ex.model.as<double>(), nullptr, nullptr);
   if (c.highpass)
-    prom::launch_highpass(st, ex.model.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(),
-                          ex.hp_g.as<double>(), ex.hp_half, ex.hp_den, ex.hp_mode, (int64_t)ex.n_exp * ex.n_trial,
-                          ex.hp_n_seg, n_pix, hp_ev ? hp_ev[0] : nullptr, hp_ev ? hp_ev[1] : nullptr);
+    highpass_launch(ex, st, ex.model.as<double>(), (int64_t)ex.n_exp * ex.n_trial, n_pix, hp_ev ? hp_ev[0] : nullptr,
+                    hp_ev ? hp_ev[1] : nullptr);
   if (c.detrend)
     prom::launch_detrend(st, ex.model.as<double>(), c.U->as<double>(), c.W->as<double>(), ex.flag.as<uint8_t>(),
                          ex.n_exp, c.n_comp, ex.n_trial, n_pix, dt_ev ? dt_ev[0] : nullptr, dt_ev ? dt_ev[1] : nullptr);
@@ -549,6 +560,31 @@ int32_t prom_highpass_set(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int
     ex.hp_half = half_width;
     ex.hp_mode = mode;
     ex.hp_den = prom::hp_den_full(g, half_width);
+    ex.hp_kind = 0;
+    ex.hp_set = true;
+  });
+}
+
+int32_t prom_highpass_set_median(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32_t* seg_first,
+                                 const int32_t* perm, int32_t half_width, int32_t mode) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    ex.hp_set = ex.hp_ran = false;
+    table_check(ctx, "prom_highpass_set_median");
+    PROM_REQUIRE(n_pix == ctx->obs.n_pix, "prom_highpass_set_median: n_pix differs from the observation's");
+    PROM_REQUIRE(n_seg >= 1 && seg_first && (n_pix == 0 || perm), "prom_highpass_set_median: segments missing");
+    PROM_REQUIRE(half_width >= 0 && half_width <= prom::kHpMaxHalf,
+                 "prom_highpass_set_median: half_width must lie in [0, 512]");
+    PROM_REQUIRE(mode == 0 || mode == 1, "prom_highpass_set_median: mode must be 0 (subtract) or 1 (divide)");
+    segments_check("prom_highpass_set_median", n_pix, n_seg, seg_first, perm);
+    const hipStream_t st = ctx->stream;
+    upload(ex.hp_seg, seg_first, (int64_t)n_seg + 1, st);
+    upload(ex.hp_perm, perm, (int64_t)n_pix, st);
+    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
+    ex.hp_n_seg = n_seg;
+    ex.hp_half = half_width;
+    ex.hp_mode = mode;
+    ex.hp_kind = 1;
     ex.hp_set = true;
   });
 }
@@ -751,8 +787,7 @@ void sysrem_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R
   if (ev) PROM_HIP(hipEventRecord(ev[1], st));
   if (ev) PROM_HIP(hipEventRecord(ev[2], st));
   if (c.highpass)
-    prom::launch_highpass(st, sy.D.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(), ex.hp_g.as<double>(),
-                          ex.hp_half, ex.hp_den, ex.hp_mode, n_exp, ex.hp_n_seg, n_pix, nullptr, nullptr);
+    highpass_launch(ex, st, sy.D.as<double>(), n_exp, n_pix);
   if (ev) PROM_HIP(hipEventRecord(ev[3], st));
   if (ev) PROM_HIP(hipEventRecord(ev[4], st));
   prom::launch_sysrem(st, sy.D.as<double>(), ex.ivar.as<double>(), sy.r.as<double>(), sy.w.as<double>(),
@@ -1065,8 +1100,7 @@ void grid_clean(prom_ctx* ctx, hipStream_t st, const double* wav, const double* 
   prom::launch_inject_grid(st, sy.raw.as<double>(), sy.model.as<double>(), sy.scale.as<double>() + b0,
                            sy.D.as<double>(), n_exp, n_pix, nb);
   if (c.highpass)
-    prom::launch_highpass(st, sy.D.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(), ex.hp_g.as<double>(),
-                          ex.hp_half, ex.hp_den, ex.hp_mode, (int64_t)nb * n_exp, ex.hp_n_seg, n_pix, nullptr, nullptr);
+    highpass_launch(ex, st, sy.D.as<double>(), (int64_t)nb * n_exp, n_pix);
   prom::launch_sysrem(st, sy.D.as<double>(), ex.ivar.as<double>(), sy.r.as<double>(), sy.w.as<double>(),
                       sy.a.as<double>(), sy.ended.as<int32_t>(), sy.part.as<double>(), sy.U.as<double>(),
                       sy.out.as<double>(), n_exp, n_pix, c.n_comp, c.n_iter, c.ones, nb);
@@ -1146,9 +1180,7 @@ void recover_grid_on(prom_ctx* ctx, hipStream_t st, const double* wav, const dou
   prom::launch_observe_q(st, wav, (int32_t)n_wav, nan, nan, ex.q.as<double>());
   expose_launch(ctx, st, wav, R, (int32_t)n_wav, false, ex.model.as<double>(), nullptr, nullptr);
   if (c.highpass)
-    prom::launch_highpass(st, ex.model.as<double>(), ex.hp_seg.as<int32_t>(), ex.hp_perm.as<int32_t>(),
-                          ex.hp_g.as<double>(), ex.hp_half, ex.hp_den, ex.hp_mode, nm, ex.hp_n_seg, n_pix, nullptr,
-                          nullptr);
+    highpass_launch(ex, st, ex.model.as<double>(), nm, n_pix);
   for (int32_t s = 0; s < prom::gr_sub_batches(g.n_inj, nb_max); ++s) {
     const int32_t b0 = prom::gr_sub_first(s, nb_max), nb = prom::gr_sub_count(s, nb_max, g.n_inj);
     grid_clean(ctx, st, wav, R, n_wav, c, b0, nb);

@@ -465,6 +465,7 @@ struct ExDev {
   // was set for does, and prom_expose_set clears hp_set.
   bool hp_set = false;
   int32_t hp_n_seg = 0, hp_half = 0, hp_mode = 0;
+  int32_t hp_kind = 0;                    // 0: the weighted mean (prom_highpass_set), 1: the median (.._set_median)
   double hp_den = 0.0;                    // hp_den_full of the taps
   DevBuf hp_seg, hp_perm, hp_g;           // seg_first[n_seg + 1], perm[n_pix] (int32), g[half_width + 1]
   bool hp_ran = false;                    // the last call on last_wav / last_R was a high-pass one ...
@@ -704,6 +705,10 @@ void launch_model_moments(hipStream_t s, const double* model, const uint8_t* fla
 void launch_highpass(hipStream_t s, double* model, const int32_t* seg_first, const int32_t* perm, const double* g,
                      int32_t half_width, double den_full, int32_t mode, int64_t n_rows, int32_t n_seg, int32_t n_pix,
                      hipEvent_t ev0, hipEvent_t ev1);
+// median high-pass (prom_median.hip): the same rows and segments with the running median over half_width positions
+// either side in the place of the weighted mean
+void launch_median(hipStream_t s, double* model, const int32_t* seg_first, const int32_t* perm, int32_t half_width,
+                   int32_t mode, int64_t n_rows, int32_t n_seg, int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1);
 // per-order moments (prom_orders.hip): the records orec[n_exp][nb][n_seg][8] of the trials [j_first, j_first + nb) of
 // the model that lies in memory, over the orders seg_first[n_seg + 1] / perm[n_pix]; then the totals
 // tot[n_exp][n_trial][4] of the same trials from the records and keep[n_seg]

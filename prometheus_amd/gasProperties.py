@@ -706,7 +706,11 @@ class _ExposeJob:
             else:
                 dev.detrend_set(self.dt.U, self.dt.W, key=self.dt.key)
         if self.hp is not None and dev.highpass_key != self.hp.key:   # (likewise)
-            dev.highpass_set(self.hp.seg_first, self.hp.perm, self.hp.taps, self.hp.mode_id, key=self.hp.key)
+            if self.hp.kind == "median":
+                dev.highpass_set_median(self.hp.seg_first, self.hp.perm, self.hp.half_width, self.hp.mode_id,
+                                        key=self.hp.key)
+            else:
+                dev.highpass_set(self.hp.seg_first, self.hp.perm, self.hp.taps, self.hp.mode_id, key=self.hp.key)
         if self.od is not None and dev.orders_key != self.od.key:   # (likewise)
             dev.orders_set(self.od.seg_first, self.od.perm, self.od.keep, key=self.od.key)
 

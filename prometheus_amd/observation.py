@@ -313,6 +313,60 @@ def box_taps(half_width: int) -> np.ndarray:
     return np.ones(h + 1)
 
 
+class MedianWindow:
+    """The window of a running median high-pass: ``half_width`` positions either side of a pixel.  Given wherever
+    taps are: high_pass(a, median_window(h), ...) and HighPass(exposures, median_window(h), ...)."""
+
+    def __init__(self, half_width: int):
+        if isinstance(half_width, (bool, np.bool_)) or not isinstance(half_width, (int, np.integer)):
+            raise ValueError("median_window: half_width must be an integer in [0, %d]" % MAX_HALF_WIDTH)
+        if not 0 <= int(half_width) <= MAX_HALF_WIDTH:
+            raise ValueError("median_window: half_width must be an integer in [0, %d]" % MAX_HALF_WIDTH)
+        self.half_width = int(half_width)
+
+    def __repr__(self):
+        return "MedianWindow(%d)" % self.half_width
+
+
+def median_window(half_width: int) -> MedianWindow:
+    """A running median over 2 half_width + 1 pixels, half_width an integer in [0, 512] (ValueError otherwise), in the
+    place of taps: the continuum is then the median of the values within half_width positions that are not NaN."""
+    return MedianWindow(half_width)
+
+
+def _median_keys(x):
+    """The order-preserving integer keys of float64 x (-0 below +0, the infinities ordinary values); a NaN gets the
+    largest key of all."""
+    b = np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+    top = np.uint64(1) << np.uint64(63)
+    return np.where(np.isnan(x), ~np.uint64(0), np.where(b >> np.uint64(63) != 0, ~b, b | top))
+
+
+def _median_values(k):
+    top = np.uint64(1) << np.uint64(63)
+    return np.where(k & top != 0, k ^ top, ~k).astype(np.uint64).view(np.float64)
+
+
+def _running_median(x, h):
+    """B of the definition (include/prom_hip.h, "median high-pass on the device") along the last axis of x[..., n]:
+    the windows clipped at the ends, NaN skipped, the values in the order of their integer keys; NaN where the
+    window holds no value."""
+    n = x.shape[-1]
+    rows = x.reshape(-1, n)
+    B = np.empty_like(rows)
+    h = min(h, max(n - 1, 0))                                    # (a wider window holds nothing more)
+    for r, row in enumerate(rows):
+        keys = np.full(n + 2 * h, ~np.uint64(0), dtype=np.uint64)
+        keys[h:h + n] = _median_keys(row)
+        win = np.sort(np.lib.stride_tricks.sliding_window_view(keys, 2 * h + 1), axis=-1)      # [n][2 h + 1]
+        c = (win != ~np.uint64(0)).sum(axis=-1)
+        pick = lambda k: _median_values(np.take_along_axis(win, np.maximum(k, 0)[:, None], axis=-1)[:, 0])
+        lo, hi = pick((c - 1) // 2), pick(c // 2)
+        with np.errstate(invalid="ignore", over="ignore"):
+            B[r] = np.where(c == 0, np.nan, np.where(c % 2 == 1, lo, (lo + hi) * 0.5))
+    return B.reshape(x.shape)
+
+
 def _check_taps(taps, who) -> np.ndarray:
     g = np.array(taps, dtype=np.float64)
     if g.ndim != 1 or not 1 <= len(g) <= MAX_HALF_WIDTH + 1:
@@ -348,14 +402,25 @@ def high_pass(a, taps, orders=None, mode: str = "subtract") -> np.ndarray:
     within half_width = len(taps) - 1 of it, weighted with taps[distance] and normalised by the weights of the
     values that are not NaN, is subtracted from the value or divided out of it; NaN stays NaN.  The sums run in
     ascending position and every product and sum is rounded on its own, which is the device's definition
-    (include/prom_hip.h, "high-pass filtered exposures on the device") bit for bit."""
-    g = _check_taps(taps, "high_pass")
+    (include/prom_hip.h, "high-pass filtered exposures on the device") bit for bit.  With a median_window in the place
+    of taps B is the running median of the values that are not NaN in the same window (the mean of the two middle
+    ones when their count is even), in the order that puts -0 below +0: "median high-pass on the device" there, bit for
+    bit."""
+    median = isinstance(taps, MedianWindow)
+    g = None if median else _check_taps(taps, "high_pass")
     m = _check_mode(mode, "high_pass")
     a = np.asarray(a, dtype=np.float64)
     if a.ndim < 1:
         raise ValueError("high_pass: a must be [..., n_pix]")
-    h = len(g) - 1
     out = np.empty_like(a)
+    if median:
+        for idx in _order_members(orders, a.shape[-1], "high_pass"):
+            x = a[..., idx]
+            with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                B = _running_median(x, taps.half_width)
+                out[..., idx] = x - B if m == 0 else x / B
+        return out
+    h = len(g) - 1
     for idx in _order_members(orders, a.shape[-1], "high_pass"):
         x = a[..., idx]
         n = len(idx)
@@ -375,7 +440,8 @@ def high_pass(a, taps, orders=None, mode: str = "subtract") -> np.ndarray:
 class HighPass:
     """The high-pass of Transit.expose(highpass=...): every exposure's model is filtered along the pixels of each
     order as high_pass filters data, on the device, before the SYSREM filter (if any) and the moments.  ``taps``:
-    gaussian_taps, box_taps or any [half_width + 1] weights (finite, >= 0, the first > 0, half_width <= 512);
+    gaussian_taps, box_taps or any [half_width + 1] weights (finite, >= 0, the first > 0, half_width <= 512), or a
+    median_window for a running median (``kind`` is then "median" and ``taps`` None, otherwise "mean");
     ``orders``: an integer label per pixel of ``exposures`` in the caller's order (None: one order); ``mode``:
     'subtract' or 'divide'.  The segments in the device's pixel order (``seg_first``, ``perm``) and the content key that
     lets a device skip the upload are computed once here; the arrays are copied.  ValueError / TypeError for bad
@@ -385,8 +451,11 @@ class HighPass:
         from .gasProperties import _content_fingerprint
         if not isinstance(exposures, Exposures):
             raise TypeError("HighPass: exposures must be an observation.Exposures")
-        self.taps = np.ascontiguousarray(_check_taps(taps, "HighPass"))
-        self.half_width = len(self.taps) - 1
+        if isinstance(taps, MedianWindow):
+            self.kind, self.taps, self.half_width = "median", None, taps.half_width
+        else:
+            self.kind, self.taps = "mean", np.ascontiguousarray(_check_taps(taps, "HighPass"))
+            self.half_width = len(self.taps) - 1
         self.mode = mode
         self.mode_id = _check_mode(mode, "HighPass")
         ins = exposures.instrument
@@ -402,7 +471,12 @@ class HighPass:
             self.seg_first = np.zeros(2, dtype=np.int32)
         self.n_seg = len(self.seg_first) - 1
         self.exposures_key = exposures.key
-        self.key = ("highpass", exposures.key, self.mode_id) + _content_fingerprint(self.taps, self.perm, self.seg_first)
+        if self.kind == "median":
+            self.key = (("highpass", exposures.key, self.mode_id, "median", self.half_width)
+                        + _content_fingerprint(self.perm, self.seg_first))
+        else:
+            self.key = (("highpass", exposures.key, self.mode_id)
+                        + _content_fingerprint(self.taps, self.perm, self.seg_first))
 
 
 class Orders:
