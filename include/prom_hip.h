@@ -912,6 +912,82 @@ int32_t prom_spectrum_recover_grid(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, 
                                    int32_t n_comp, int32_t n_iter, int32_t ones, int32_t orders, double* mom_out,
                                    int64_t* n_used_out, double* tot_out, double* U_out);
 
+/* ---- SYSREM per order on the device ---------------------------------------------------------------
+ * Every high-resolution pipeline runs SYSREM one echelle order at a time: each order has its own telluric and blaze
+ * systematics and so its own basis U.  The calls here clean every resident order on its own in the launches of ONE
+ * single call: an order is one more batch item of the SYSREM kernels, as an injection is in the grids.
+ *
+ *   orders               the resident orders of prom_orders_set (n_seg, seg_first, perm) cut the pixels into orders.
+ *                        keep plays no part: every order is cleaned.  Order s has n_s = seg_first[s + 1] - seg_first[s]
+ *                        positions, in the order perm gives them
+ *   injection, high-pass D, the optional resident high-pass of D and `injected` are exactly what the single call forms
+ *                        ("injection and SYSREM on the device").  They are not per order: the high-pass keeps its own
+ *                        segments
+ *   SYSREM per order     for order s the weights, fit_c, fit_a, the norm, ended components and the subtraction are the
+ *                        single call's definition, word for word, on the table whose columns are the pixels
+ *                        perm[seg_first[s] + i], i = 0 .. n_s - 1, with n_pix = n_s.  In particular the shape of a
+ *                        row sum is a function of n_s alone
+ *   outputs              U_out[n_seg][n_exp][n_comp + ones] (a leading [n_inj] for the grids); cleaned[e][p] comes
+ *                        from p's own order; injected as the single call's
+ *   independence         order s's numbers do not depend on the other orders, on n_seg or on where s sits.  A
+ *                        component that ends in one order ends there alone.  With one order and the identity perm
+ *                        everything equals the single call bit for bit
+ *   layout               batch item y = b n_seg + s of the work buffers is order s of injection b; every item is
+ *                        n_max = max n_s wide.  Padding an order from n_s to n_max appends groups and tiles whose sums
+ *                        are +0; every sum starts at +0 and so is never -0, and adding +0 leaves its bits: the padded
+ *                        item's row sums are the single call's on n_s pixels.  Unequal orders pay for the padding
+ *                        (echelle orders have equal pixel counts); there is no compacted layout
+ *   launches             those of one single call, 2 + n_cols + n_comp (2 n_iter + 1), whatever n_seg
+ *   errors               the namesake's, and PROM_E_STATE without resident orders; PROM_E_ARG for more than 65,535
+ *                        orders
+ *   sub-batches (grids)  as the grids', with the per-injection bytes of n_seg items n_max wide, and
+ *                        n_inj_sub n_seg <= 65,535
+ *   no pixel             n_pix = 0: U is zeros behind the column of ones for the one order
+ *   afterwards           prom_sysrem_kernel_ms repeats a per-order clean or inject call as it repeats the single ones */
+int32_t prom_sysrem_clean_orders(prom_ctx* ctx, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones,
+                                 double* U_out, double* cleaned_out, double* injected_out);
+int32_t prom_transit_inject_orders(prom_ctx* ctx, int32_t trial, double scale, int32_t highpass, int32_t n_comp,
+                                   int32_t n_iter, int32_t ones, double* U_out, double* cleaned_out,
+                                   double* injected_out);
+int32_t prom_spectrum_inject_orders(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                    int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter,
+                                    int32_t ones, double* U_out, double* cleaned_out, double* injected_out);
+int32_t prom_transit_inject_grid_orders(prom_ctx* ctx, int32_t n_inj, const int32_t* trial, const double* scale,
+                                        int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out,
+                                        double* cleaned_out, double* injected_out);
+int32_t prom_spectrum_inject_grid_orders(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                         int32_t n_inj, const int32_t* trial, const double* scale, int32_t highpass,
+                                         int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out,
+                                         double* cleaned_out, double* injected_out);
+
+/* The filter per order.  The filter is given U[n_seg][n_exp][K], a basis per order, and seg_of[n_pix], the order of
+ * every device pixel (0 <= seg_of[p] < n_seg).
+ *
+ *   weights              at pixel p of order s, W[.][.][p] is "the filter's weights on the device" with U_s: a pixel's
+ *                        bits equal the single-basis call given U_s
+ *   filtered model       M' at p is "detrended exposures on the device" (the coefficients W_p M, then M - U c) with
+ *                        U_s, bit for bit
+ *   kernels              the existing function text with the U pointer moved per lane by seg_of[p] n_exp K; U is then a
+ *                        vector load, no longer a scalar one.  No instantiation uses scratch (profiles/)
+ *   resident filter      prom_detrend_set_orders / prom_detrend_build_orders make a per-order filter resident for the
+ *                        resident orders: seg_of is formed from their perm at that moment.  After them every
+ *                        detrended, high-pass (detrend = 1) and per-order-moments (detrend = 1) call filters with it.
+ *                        prom_detrend_set or prom_detrend_build puts a single basis back; prom_orders_set drops a
+ *                        per-order filter (the calls that need one then fail with PROM_E_STATE), and so does whatever
+ *                        drops the exposure table
+ *   errors               those of the single-basis namesakes; PROM_E_STATE without resident orders; PROM_E_ARG when
+ *                        n_seg differs from the resident orders' or seg_of leaves [0, n_seg) */
+
+/* The definition on arrays the caller supplies (no table is needed): W_out[n_comp][n_exp][n_pix]. */
+int32_t prom_filter_weights_orders(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, int32_t n_pix, int32_t n_seg,
+                                   const int32_t* seg_of, const double* U, const double* ivar, double* W_out);
+/* Make the per-order filter (U[n_seg][n_exp][n_comp], W[n_comp][n_exp][n_pix]) resident. */
+int32_t prom_detrend_set_orders(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, int32_t n_seg, const double* U,
+                                const double* W);
+/* The same with W formed on the device over the table's ivar; it comes back in W_out unless that is NULL. */
+int32_t prom_detrend_build_orders(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, int32_t n_seg, const double* U,
+                                  double* W_out);
+
 /* Per-kernel device durations of the transit path (ABI 5; ids 5 and 6 since ABI 6): n_runs runs of the current problem, one at a
  * time (one slot, no second stream; the stream waits after every run), each kernel timed by start/stop
  * events on its own dispatch packet (groups of kernels: the first start to the last stop).  ms_out[k] is

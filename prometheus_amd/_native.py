@@ -183,6 +183,19 @@ SIGNATURES = {
     "prom_spectrum_recover_grid": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _ip, _dp,
                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp,
                                                C.POINTER(C.c_int64), _dp, _dp]),
+    "prom_sysrem_clean_orders": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "prom_transit_inject_orders": (C.c_int32, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, _dp, _dp, _dp]),
+    "prom_spectrum_inject_orders": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, C.c_double,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "prom_transit_inject_grid_orders": (C.c_int32, [C.c_void_p, C.c_int32, _ip, _dp, C.c_int32, C.c_int32, C.c_int32,
+                                                    C.c_int32, _dp, _dp, _dp]),
+    "prom_spectrum_inject_grid_orders": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _ip, _dp,
+                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "prom_filter_weights_orders": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _ip, _dp, _dp,
+                                               _dp]),
+    "prom_detrend_set_orders": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]),
+    "prom_detrend_build_orders": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]),
     "prom_star_disk_flux": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double,
                                         C.c_int64, _dp, _dp]),
     "prom_timing_begin": (C.c_int32, [C.c_void_p]),
@@ -320,6 +333,7 @@ class Device:
         self._od_n_seg = 0
         self._br_key = None
         self._sy_key = None
+        self._dt_per_order = False   # the resident filter is a per-order one (orders_set then drops it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -710,6 +724,7 @@ class Device:
         self._dt_key = None
         self._check(self.lib.prom_detrend_set(self.h, n_exp, n_comp, _d(U), _d(W)), "prom_detrend_set")
         self._dt_key = key
+        self._dt_per_order = False
 
     @property
     def detrend_key(self):
@@ -812,6 +827,8 @@ class Device:
         if kp.shape != (len(seg) - 1,):
             raise ValueError("orders_set: keep must be [n_seg]")
         self._od_key = None
+        if self._dt_per_order:   # (new orders drop a per-order filter)
+            self._dt_key = None
         ip = C.POINTER(C.c_int32)
         self._check(self.lib.prom_orders_set(self.h, len(pm), len(seg) - 1, seg.ctypes.data_as(ip),
                                              pm.ctypes.data_as(ip), kp.ctypes.data_as(C.POINTER(C.c_uint8))),
@@ -925,9 +942,11 @@ class Device:
         """The ``key`` of the raw exposures resident on the context (None: none, or set without a key)."""
         return self._sy_key
 
-    def _sysrem_outputs(self, n_comp: int, ones: bool, injected: bool):
+    def _sysrem_outputs(self, n_comp: int, ones: bool, injected: bool, orders: bool = False):
         n_exp, _, n_pix = self._ex_shape or (0, 0, 0)
         U = np.zeros((n_exp, max(int(n_comp) + int(bool(ones)), 0)))
+        if orders:   # (per order: a basis per resident order)
+            U = np.zeros((self._od_n_seg,) + U.shape)
         cleaned = np.full((n_exp, n_pix), np.nan)
         inj = np.full((n_exp, n_pix), np.nan) if injected else None
         return (U, cleaned, inj), (_d(U), _d(cleaned), _d(inj) if injected else None)
@@ -958,6 +977,35 @@ class Device:
         self._check(self.lib.prom_spectrum_inject(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(trial), float(scale),
                                                   int(bool(highpass)), int(n_comp), int(n_iter), int(bool(ones)), *ptr),
                     "prom_spectrum_inject")
+        return out
+
+    # ---- SYSREM per order (prom_hip.h "SYSREM per order on the device") ---------------------------
+    def sysrem_clean_orders(self, n_comp: int, n_iter: int = 30, ones: bool = False, highpass: bool = False,
+                            injected: bool = False):
+        """prom_sysrem_clean_orders: sysrem_clean with every resident order (orders_set) cleaned on its own, in the
+        launches of one call: (U [n_seg][n_exp][n_comp + ones], cleaned, injected or None)."""
+        out, ptr = self._sysrem_outputs(n_comp, ones, injected, orders=True)
+        self._check(self.lib.prom_sysrem_clean_orders(self.h, int(bool(highpass)), int(n_comp), int(n_iter),
+                                                      int(bool(ones)), *ptr), "prom_sysrem_clean_orders")
+        return out
+
+    def transit_inject_orders(self, trial: int, scale: float, n_comp: int, n_iter: int = 30, ones: bool = False,
+                              highpass: bool = False, injected: bool = False):
+        """prom_transit_inject_orders: transit_inject with every resident order cleaned on its own."""
+        out, ptr = self._sysrem_outputs(n_comp, ones, injected, orders=True)
+        self._check(self.lib.prom_transit_inject_orders(self.h, int(trial), float(scale), int(bool(highpass)),
+                                                        int(n_comp), int(n_iter), int(bool(ones)), *ptr),
+                    "prom_transit_inject_orders")
+        return out
+
+    def spectrum_inject_orders(self, wav, R, trial: int, scale: float, n_comp: int, n_iter: int = 30,
+                               ones: bool = False, highpass: bool = False, injected: bool = False):
+        """prom_spectrum_inject_orders: the same for R[n_orb][n_wav] on the ascending grid wav."""
+        wav, R = _spectrum(wav, R, "spectrum_inject_orders")
+        out, ptr = self._sysrem_outputs(n_comp, ones, injected, orders=True)
+        self._check(self.lib.prom_spectrum_inject_orders(self.h, R.shape[0], len(wav), _d(wav), _d(R), int(trial),
+                                                         float(scale), int(bool(highpass)), int(n_comp), int(n_iter),
+                                                         int(bool(ones)), *ptr), "prom_spectrum_inject_orders")
         return out
 
     def sysrem_kernel_ms(self, n_runs: int = 5):
@@ -994,6 +1042,54 @@ class Device:
         self._check(self.lib.prom_detrend_build(self.h, n_exp, n_comp, _d(U), _d(W) if weights else None),
                     "prom_detrend_build")
         self._dt_key = key
+        self._dt_per_order = False
+        return W
+
+    # ---- the filter per order (prom_hip.h "SYSREM per order on the device") -----------------------
+    def filter_weights_orders(self, U, ivar, seg_of) -> np.ndarray:
+        """prom_filter_weights_orders: W [n_comp][n_exp][n_pix] of U [n_seg][n_exp][n_comp], ivar [n_exp][n_pix] and
+        seg_of [n_pix] (int32, the order of every pixel): pixel p is given the basis U[seg_of[p]]."""
+        U, ivar = _f64(U), _f64(ivar)
+        sg = np.ascontiguousarray(seg_of, dtype=np.int32)
+        if U.ndim != 3 or ivar.ndim != 2 or ivar.shape[0] != U.shape[1] or sg.shape != (ivar.shape[1],):
+            raise ValueError("filter_weights_orders: U must be [n_seg][n_exp][n_comp], ivar [n_exp][n_pix] and seg_of "
+                             "[n_pix]")
+        n_seg, n_exp, n_comp = U.shape
+        W = np.zeros((n_comp, n_exp, ivar.shape[1]))
+        self._check(self.lib.prom_filter_weights_orders(self.h, n_exp, n_comp, ivar.shape[1], n_seg,
+                                                        sg.ctypes.data_as(_ip), _d(U), _d(ivar), _d(W)),
+                    "prom_filter_weights_orders")
+        return W
+
+    def detrend_set_orders(self, U, W, key=None) -> None:
+        """prom_detrend_set_orders: the per-order filter of the resident exposure table: U [n_seg][n_exp][n_comp], a
+        basis per resident order (orders_set), and W [n_comp][n_exp][n_pix] in the device's pixel order.  Every
+        detrended call afterwards filters pixel p with the basis of its own order; detrend_set / detrend_build put the
+        single basis back, orders_set drops the filter.  ``key``: as detrend_set's."""
+        U, W = _f64(U), _f64(W)
+        if U.ndim != 3 or W.ndim != 3 or W.shape[:2] != (U.shape[2], U.shape[1]):
+            raise ValueError("detrend_set_orders: U must be [n_seg][n_exp][n_comp] and W [n_comp][n_exp][n_pix]")
+        self._dt_key = None
+        n_seg, n_exp, n_comp = U.shape
+        self._check(self.lib.prom_detrend_set_orders(self.h, n_exp, n_comp, n_seg, _d(U), _d(W)),
+                    "prom_detrend_set_orders")
+        self._dt_key = key
+        self._dt_per_order = True
+
+    def detrend_build_orders(self, U, key=None, weights: bool = False):
+        """prom_detrend_build_orders: the per-order filter from U [n_seg][n_exp][n_comp] alone; W is formed on the
+        device over the table's ivar, every pixel with its own order's basis, and returned with ``weights``."""
+        U = _f64(U)
+        if U.ndim != 3:
+            raise ValueError("detrend_build_orders: U must be [n_seg][n_exp][n_comp]")
+        n_seg, n_exp, n_comp = U.shape
+        n_pix = (self._ex_shape or (0, 0, 0))[2]
+        W = np.zeros((n_comp, n_exp, n_pix)) if weights else None
+        self._dt_key = None
+        self._check(self.lib.prom_detrend_build_orders(self.h, n_exp, n_comp, n_seg, _d(U),
+                                                       _d(W) if weights else None), "prom_detrend_build_orders")
+        self._dt_key = key
+        self._dt_per_order = True
         return W
 
     def filter_kernel_ms(self, n_runs: int = 20) -> float:
@@ -1046,9 +1142,10 @@ class Device:
             raise ValueError("%s: trials and scales must be two lists of one length" % who)
         return len(t), t, s
 
-    def _inject_grid_outputs(self, n_inj: int, n_comp: int, ones: bool, data: bool, injected: bool):
+    def _inject_grid_outputs(self, n_inj: int, n_comp: int, ones: bool, data: bool, injected: bool,
+                             orders: bool = False):
         n_exp, _, n_pix = self._ex_shape or (0, 0, 0)
-        U = np.zeros((n_inj, n_exp, max(int(n_comp) + int(bool(ones)), 0)))
+        U = np.zeros((n_inj,) + ((self._od_n_seg,) if orders else ()) + (n_exp, max(int(n_comp) + int(bool(ones)), 0)))
         cleaned = np.full((n_inj, n_exp, n_pix), np.nan) if data else None
         inj = np.full((n_inj, n_exp, n_pix), np.nan) if injected else None
         return (U, cleaned, inj), (_d(U), _d(cleaned) if data else None, _d(inj) if injected else None)
@@ -1075,6 +1172,29 @@ class Device:
                                                        t.ctypes.data_as(_ip), _d(s), int(bool(highpass)), int(n_comp),
                                                        int(n_iter), int(bool(ones)), *ptr),
                     "prom_spectrum_inject_grid")
+        return out
+
+    def transit_inject_grid_orders(self, trials, scales, n_comp: int, n_iter: int = 30, ones: bool = False,
+                                   highpass: bool = False, data: bool = True, injected: bool = False):
+        """prom_transit_inject_grid_orders: transit_inject_grid with every resident order cleaned on its own: U is
+        [n_inj][n_seg][n_exp][n_comp + ones], entry b what transit_inject_orders gives for that point."""
+        n_inj, t, s = self._grid_list(trials, scales, "transit_inject_grid_orders")
+        out, ptr = self._inject_grid_outputs(n_inj, n_comp, ones, data, injected, orders=True)
+        self._check(self.lib.prom_transit_inject_grid_orders(self.h, n_inj, t.ctypes.data_as(_ip), _d(s),
+                                                             int(bool(highpass)), int(n_comp), int(n_iter),
+                                                             int(bool(ones)), *ptr), "prom_transit_inject_grid_orders")
+        return out
+
+    def spectrum_inject_grid_orders(self, wav, R, trials, scales, n_comp: int, n_iter: int = 30, ones: bool = False,
+                                    highpass: bool = False, data: bool = True, injected: bool = False):
+        """prom_spectrum_inject_grid_orders: the same for R[n_orb][n_wav] on the ascending grid wav."""
+        wav, R = _spectrum(wav, R, "spectrum_inject_grid_orders")
+        n_inj, t, s = self._grid_list(trials, scales, "spectrum_inject_grid_orders")
+        out, ptr = self._inject_grid_outputs(n_inj, n_comp, ones, data, injected, orders=True)
+        self._check(self.lib.prom_spectrum_inject_grid_orders(self.h, R.shape[0], len(wav), _d(wav), _d(R), n_inj,
+                                                              t.ctypes.data_as(_ip), _d(s), int(bool(highpass)),
+                                                              int(n_comp), int(n_iter), int(bool(ones)), *ptr),
+                    "prom_spectrum_inject_grid_orders")
         return out
 
     def _recover_grid_outputs(self, n_inj: int, n_comp: int, ones: bool, orders: bool, moments: bool, totals: bool):

@@ -18,7 +18,7 @@ HEADERS = ["../include/prom_hip.h", "csrc/prom_internal.h", "csrc/prom_api_share
            "csrc/prom_tc.h", "csrc/tc_phase.h", "csrc/tw_index.h", "csrc/tw_stage.h",
            "csrc/obs_index.h", "csrc/vmap_index.h", "csrc/expose_index.h", "csrc/detrend_index.h",
            "csrc/highpass_index.h", "csrc/median_index.h", "csrc/order_index.h", "csrc/broaden_index.h", "csrc/sysrem_index.h",
-           "csrc/filter_index.h", "csrc/grid_index.h", "csrc/faddeeva.h", "csrc/exp2_table.h", "csrc/exp2_table_body.h"]
+           "csrc/filter_index.h", "csrc/grid_index.h", "csrc/order_sysrem_index.h", "csrc/faddeeva.h", "csrc/exp2_table.h", "csrc/exp2_table_body.h"]
 OUT = os.path.join(HERE, "libprom_hip.so")
 ARCH = os.environ.get("PROM_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=" + ARCH, "-ffp-contract=off", "-fPIC", "-Wall",

@@ -13,6 +13,7 @@
 #include "sysrem_index.h"
 #include "filter_index.h"
 #include "grid_index.h"
+#include "order_sysrem_index.h"
 
 namespace {
 
@@ -190,13 +191,16 @@ struct ChainCall {
   bool always;                      // the call runs whatever the outputs (the recovery)
   const char* noun;                 // the out-of-memory message's "<noun> the model of all ... trials"
   ExOut out;
+  const int32_t* seg_of;            // a per-order filter: U is [n_seg][n_exp][n_comp] and pixel p takes the basis of
+                                    // order seg_of[p] (on the device); left out or null: one basis
 };
 
 // a call on the resident filter and the table's own data
 ChainCall resident_call(prom_ctx* ctx, bool highpass, bool detrend, bool orders, Ran ran, const char* noun,
                         const ExOut& out) {
   prom::ExDev& ex = ctx->ex;
-  return ChainCall{highpass, detrend, orders, &ex.U, &ex.W, ex.n_comp, &ex.data, ran, false, noun, out};
+  return ChainCall{highpass, detrend, orders, &ex.U, &ex.W, ex.n_comp, &ex.data, ran, false, noun, out,
+                   ex.dt_n_seg > 0 ? ex.dt_seg_of.as<int32_t>() : nullptr};
 }
 
 // the moments of the model in ex.model against `data`, in batches of whole trial groups (ev: events around the first
@@ -318,7 +322,8 @@ void chain_model(prom_ctx* ctx, hipStream_t st, const ChainCall& c, const double
                     hp_ev ? hp_ev[1] : nullptr);
   if (c.detrend)
     prom::launch_detrend(st, ex.model.as<double>(), c.U->as<double>(), c.W->as<double>(), ex.flag.as<uint8_t>(),
-                         ex.n_exp, c.n_comp, ex.n_trial, n_pix, dt_ev ? dt_ev[0] : nullptr, dt_ev ? dt_ev[1] : nullptr);
+                         ex.n_exp, c.n_comp, ex.n_trial, n_pix, dt_ev ? dt_ev[0] : nullptr, dt_ev ? dt_ev[1] : nullptr,
+                         nullptr, c.seg_of);
   else
     PROM_HIP(hipMemsetAsync(ex.flag.as<uint8_t>(), 1, (size_t)ex.n_trial * n_pix, st));
 }
@@ -491,6 +496,53 @@ int32_t prom_detrend_set(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, const dou
     upload(ex.W, W, nw, st);
     PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
     ex.n_comp = n_comp;
+    ex.dt_n_seg = 0;
+    ex.dt_set = true;
+  });
+}
+
+namespace {
+
+// what the two per-order filter sets share: the checks, seg_of of the resident orders and U[n_seg][n_exp][n_comp] on
+// the device; the filter is not resident until the caller says so
+void detrend_orders_begin(prom_ctx* ctx, const char* who, int32_t n_exp, int32_t n_comp, int32_t n_seg, const double* U,
+                          hipStream_t st) {
+  prom::ExDev& ex = ctx->ex;
+  const std::string w(who);
+  ex.dt_set = ex.dt_ran = false;
+  ex.dt_n_seg = 0;
+  if (ctx->rc.last == 1) ctx->rc.last = 0;
+  table_check(ctx, who);
+  if (!ex.od_set) throw Error(PROM_E_STATE, w + ": no orders on the context (prom_orders_set)");
+  PROM_REQUIRE(n_exp == ex.n_exp, w + ": n_exp differs from the exposure table's");
+  PROM_REQUIRE(n_comp >= 1 && n_comp <= prom::kDtMaxComp, w + ": n_comp must lie in [1, 16]");
+  PROM_REQUIRE(n_seg == ex.od_n_seg, w + ": n_seg differs from the resident orders'");
+  const int64_t nu = (int64_t)n_seg * n_exp * n_comp;
+  PROM_REQUIRE(U, w + ": U missing");
+  for (int64_t i = 0; i < nu; ++i) PROM_REQUIRE(obs_finite(U[i]), w + ": U must be finite");
+  const int32_t n_pix = ctx->obs.n_pix;
+  std::vector<int32_t> seg_of((size_t)std::max(n_pix, 1), 0);
+  prom::fo_seg_of(n_seg, ex.od_seg_host.data(), ex.od_perm_host.data(), seg_of.data());
+  upload(ex.U, U, nu, st);
+  upload(ex.dt_seg_of, seg_of.data(), (int64_t)n_pix, st);
+  PROM_HIP(hipStreamSynchronize(st));   // (seg_of is a local; U is read during the call only)
+}
+
+}  // namespace
+
+int32_t prom_detrend_set_orders(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, int32_t n_seg, const double* U,
+                                const double* W) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    const hipStream_t st = ctx->stream;
+    const int64_t nw = (int64_t)n_comp * n_exp * ctx->obs.n_pix;
+    detrend_orders_begin(ctx, "prom_detrend_set_orders", n_exp, n_comp, n_seg, U, st);
+    PROM_REQUIRE(nw == 0 || W, "prom_detrend_set_orders: W missing");
+    for (int64_t i = 0; i < nw; ++i) PROM_REQUIRE(obs_finite(W[i]), "prom_detrend_set_orders: W must be finite");
+    upload(ex.W, W, nw, st);
+    PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
+    ex.n_comp = n_comp;
+    ex.dt_n_seg = n_seg;
     ex.dt_set = true;
   });
 }
@@ -633,6 +685,11 @@ int32_t prom_orders_set(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32
   return guarded(ctx, [&] {
     prom::ExDev& ex = ctx->ex;
     ex.od_set = ex.od_ran = false;
+    if (ex.dt_n_seg > 0) {   // a per-order filter belongs to the orders it was set for
+      ex.dt_set = ex.dt_ran = false;
+      ex.dt_n_seg = 0;
+      if (ctx->rc.last == 1) ctx->rc.last = 0;
+    }
     table_check(ctx, "prom_orders_set");
     PROM_REQUIRE(n_pix == ctx->obs.n_pix, "prom_orders_set: n_pix differs from the observation's");
     PROM_REQUIRE(n_seg >= 1 && seg_first && keep && (n_pix == 0 || perm), "prom_orders_set: orders missing");
@@ -644,6 +701,9 @@ int32_t prom_orders_set(prom_ctx* ctx, int32_t n_pix, int32_t n_seg, const int32
     upload(ex.od_keep, keep, (int64_t)n_seg, st);
     PROM_HIP(hipStreamSynchronize(st));   // the host arrays are read during the call only
     ex.od_n_seg = n_seg;
+    ex.od_n_max = prom::os_n_max(n_seg, seg_first);
+    ex.od_seg_host.assign(seg_first, seg_first + n_seg + 1);
+    ex.od_perm_host.assign(perm, perm + n_pix);
     ex.od_set = true;
   });
 }
@@ -716,7 +776,12 @@ namespace {
 struct SyCall {
   int32_t source, trial, highpass, n_comp, n_iter, ones;
   double scale;
+  int32_t orders;   // 1: SYSREM per resident order (prom_orders_set), U gains the order dimension (left out: 0)
 };
+
+// the batch items of one injection and their width: the resident orders and the longest of them, or the table
+int32_t sy_items(const prom_ctx* ctx, const SyCall& c) { return c.orders ? ctx->ex.od_n_seg : 1; }
+int32_t sy_width(const prom_ctx* ctx, const SyCall& c) { return c.orders ? ctx->ex.od_n_max : ctx->sy.n_pix; }
 
 void sysrem_check(prom_ctx* ctx, const char* who, const SyCall& c) {
   const std::string w(who);
@@ -735,6 +800,10 @@ void sysrem_check(prom_ctx* ctx, const char* who, const SyCall& c) {
   }
   if (c.highpass && !ctx->ex.hp_set)
     throw Error(PROM_E_STATE, w + ": highpass = 1 without a high-pass on the context (prom_highpass_set)");
+  if (c.orders && !ctx->ex.od_set)
+    throw Error(PROM_E_STATE, w + ": no orders on the context (prom_orders_set)");
+  if (c.orders && ctx->ex.od_n_seg > prom::kGrMaxBatch)
+    throw Error(PROM_E_ARG, w + ": more than 65535 orders");
 }
 
 // the shared tail of the clean / inject calls on stream st (ev: six events around the injection, the high-pass and
@@ -746,26 +815,27 @@ void sysrem_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R
   prom::ExDev& ex = ctx->ex;
   const prom::ObsDev& ob = ctx->obs;
   const int32_t n_exp = sy.n_exp, n_pix = sy.n_pix, n_cols = c.n_comp + c.ones;
+  const int32_t items = sy_items(ctx, c), width = sy_width(ctx, c);   // (per order: the orders, n_max wide)
   const int64_t n = (int64_t)n_exp * n_pix;
   if (n_pix == 0) {   // no pixel: every component ends at once
     if (U_out)
-      for (int32_t e = 0; e < n_exp; ++e)
-        for (int32_t k = 0; k < n_cols; ++k) U_out[prom::sy_u(e, k, n_cols)] = (c.ones && k == 0) ? 1.0 : 0.0;
+      for (int64_t e = 0; e < (int64_t)items * n_exp; ++e)
+        for (int32_t k = 0; k < n_cols; ++k) U_out[e * n_cols + k] = (c.ones && k == 0) ? 1.0 : 0.0;
     return;
   }
   if (wait && !ev && !U_out && !cleaned_out && !injected_out) return;
   if (ctx->rc.last == 2) ctx->rc.last = 0;   // (U may move or change its shape)
   if (c.highpass && prom::hp_workgroups(n_exp, ex.hp_n_seg) > kMaxGrid)   // (before anything is launched)
     throw Error(PROM_E_ARG, "k_highpass: n_exp n_seg too large for one launch");
-  const int64_t pitch = prom::sy_pitch(n_pix);
+  const int64_t pitch = prom::sy_pitch(width);
   sy.D.ensure(sizeof(double) * (size_t)n);
   sy.out.ensure(sizeof(double) * (size_t)n);
-  sy.r.ensure(sizeof(double) * (size_t)(n_exp * pitch));
-  sy.w.ensure(sizeof(double) * (size_t)(n_exp * pitch));
-  sy.a.ensure(sizeof(double) * (size_t)n_exp);
-  sy.ended.ensure(sizeof(int32_t) * (prom::kSyMaxComp + 1));
-  sy.part.ensure(2 * sizeof(double) * (size_t)n_exp * prom::sy_tiles(n_pix));
-  sy.U.ensure(sizeof(double) * (size_t)n_exp * n_cols);
+  sy.r.ensure(sizeof(double) * (size_t)items * (size_t)(n_exp * pitch));
+  sy.w.ensure(sizeof(double) * (size_t)items * (size_t)(n_exp * pitch));
+  sy.a.ensure(sizeof(double) * (size_t)items * n_exp);
+  sy.ended.ensure(sizeof(int32_t) * (size_t)items * prom::kGrFlags);
+  sy.part.ensure(2 * sizeof(double) * (size_t)items * n_exp * prom::sy_tiles(width));
+  sy.U.ensure(sizeof(double) * (size_t)items * n_exp * n_cols);
   if (ev) PROM_HIP(hipEventRecord(ev[0], st));
   if (c.source != 1) {
     // the model of trial `trial` alone: its factors as a table of one trial, through k_expose unchanged
@@ -790,9 +860,15 @@ void sysrem_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R
     highpass_launch(ex, st, sy.D.as<double>(), n_exp, n_pix);
   if (ev) PROM_HIP(hipEventRecord(ev[3], st));
   if (ev) PROM_HIP(hipEventRecord(ev[4], st));
-  prom::launch_sysrem(st, sy.D.as<double>(), ex.ivar.as<double>(), sy.r.as<double>(), sy.w.as<double>(),
-                      sy.a.as<double>(), sy.ended.as<int32_t>(), sy.part.as<double>(), sy.U.as<double>(),
-                      sy.out.as<double>(), n_exp, n_pix, c.n_comp, c.n_iter, c.ones);
+  if (c.orders)
+    prom::launch_sysrem_orders(st, sy.D.as<double>(), ex.ivar.as<double>(), ex.od_seg.as<int32_t>(),
+                               ex.od_perm.as<int32_t>(), sy.r.as<double>(), sy.w.as<double>(), sy.a.as<double>(),
+                               sy.ended.as<int32_t>(), sy.part.as<double>(), sy.U.as<double>(), sy.out.as<double>(),
+                               n_exp, n_pix, items, width, c.n_comp, c.n_iter, c.ones);
+  else
+    prom::launch_sysrem(st, sy.D.as<double>(), ex.ivar.as<double>(), sy.r.as<double>(), sy.w.as<double>(),
+                        sy.a.as<double>(), sy.ended.as<int32_t>(), sy.part.as<double>(), sy.U.as<double>(),
+                        sy.out.as<double>(), n_exp, n_pix, c.n_comp, c.n_iter, c.ones);
   if (ev) PROM_HIP(hipEventRecord(ev[5], st));
   sy.last_source = c.source;
   sy.last_trial = c.trial;
@@ -802,7 +878,8 @@ void sysrem_on(prom_ctx* ctx, hipStream_t st, const double* wav, const double* R
   sy.last_n_iter = c.n_iter;
   sy.last_ones = c.ones;
   sy.last_n_wav = n_wav;
-  if (U_out) download(U_out, sy.U, (int64_t)n_exp * n_cols, st);
+  sy.last_orders = c.orders;
+  if (U_out) download(U_out, sy.U, (int64_t)items * n_exp * n_cols, st);
   if (cleaned_out) download(cleaned_out, sy.out, n, st);
   if (injected_out) download(injected_out, sy.D, n, st);
   if (wait) PROM_HIP(hipStreamSynchronize(st));
@@ -841,18 +918,52 @@ int32_t prom_spectrum_inject(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const 
   });
 }
 
+// SYSREM per order: the same calls with every resident order (prom_orders_set) cleaned on its own; U_out gains the
+// order dimension, [n_seg][n_exp][n_comp + ones]
+int32_t prom_sysrem_clean_orders(prom_ctx* ctx, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones,
+                                 double* U_out, double* cleaned_out, double* injected_out) {
+  return guarded(ctx, [&] {
+    const SyCall c{1, 0, highpass, n_comp, n_iter, ones, 0.0, 1};
+    sysrem_check(ctx, "prom_sysrem_clean_orders", c);
+    sysrem_on(ctx, ctx->stream, nullptr, nullptr, 0, c, U_out, cleaned_out, injected_out, nullptr);
+  });
+}
+
+int32_t prom_transit_inject_orders(prom_ctx* ctx, int32_t trial, double scale, int32_t highpass, int32_t n_comp,
+                                   int32_t n_iter, int32_t ones, double* U_out, double* cleaned_out,
+                                   double* injected_out) {
+  return guarded(ctx, [&] {
+    const SyCall c{2, trial, highpass, n_comp, n_iter, ones, scale, 1};
+    sysrem_check(ctx, "prom_transit_inject_orders", c);
+    const TransitArgs t = ex_transit(ctx, "prom_transit_inject_orders");
+    sysrem_on(ctx, t.st, t.wav, t.R, t.n_wav, c, U_out, cleaned_out, injected_out, nullptr);
+  });
+}
+
+int32_t prom_spectrum_inject_orders(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                    int32_t trial, double scale, int32_t highpass, int32_t n_comp, int32_t n_iter,
+                                    int32_t ones, double* U_out, double* cleaned_out, double* injected_out) {
+  return guarded(ctx, [&] {
+    prom::SyDev& sy = ctx->sy;
+    const SyCall c{3, trial, highpass, n_comp, n_iter, ones, scale, 1};
+    sysrem_check(ctx, "prom_spectrum_inject_orders", c);
+    const hipStream_t st = sy_spectrum(ctx, "prom_spectrum_inject_orders", n_orb, n_wav, wav, R);
+    sysrem_on(ctx, st, sy.wav.as<double>(), sy.R.as<double>(), n_wav, c, U_out, cleaned_out, injected_out, nullptr);
+  });
+}
+
 int32_t prom_sysrem_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
   return guarded(ctx, [&] {
     prom::SyDev& sy = ctx->sy;
     prom::TransitDev& tr = ctx->tr;
     PROM_REQUIRE(n_runs >= 1 && ms_out, "prom_sysrem_kernel_ms: bad arguments");
     const bool table = table_present(ctx) && sy.set && sy.n_pix > 0;
-    if (!table || sy.last_source == 0 || (sy.last_highpass && !ctx->ex.hp_set) ||
+    if (!table || sy.last_source == 0 || (sy.last_highpass && !ctx->ex.hp_set) || (sy.last_orders && !ctx->ex.od_set) ||
         (sy.last_source == 2 && (!tr.ran || ctx->ex.n_orb != tr.n_orb || tr.n_wav != sy.last_n_wav)) ||
         (sy.last_source == 3 && sy.last_n_orb != ctx->ex.n_orb))
       throw Error(PROM_E_STATE, "prom_sysrem_kernel_ms: no clean or inject call to repeat");
     const SyCall c{sy.last_source, sy.last_trial, sy.last_highpass, sy.last_n_comp, sy.last_n_iter, sy.last_ones,
-                   sy.last_scale};
+                   sy.last_scale, sy.last_orders};
     const double* wav = c.source == 2 ? tr.wav.as<double>() : sy.wav.as<double>();
     const double* R = c.source == 2 ? transit_R(ctx) : sy.R.as<double>();
     double sum[3];   // the injection, the high-pass, SYSREM
@@ -907,6 +1018,56 @@ int32_t prom_detrend_build(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, const d
     if (W_out) download(W_out, ex.W, nw, st);
     PROM_HIP(hipStreamSynchronize(st));   // the host array is read during the call only
     ex.n_comp = n_comp;
+    ex.dt_n_seg = 0;
+    ex.dt_set = true;
+    if (n_pix > 0) {
+      ctx->rc.last = 1;
+      ctx->rc.last_n_comp = n_comp;
+    }
+  });
+}
+
+int32_t prom_filter_weights_orders(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, int32_t n_pix, int32_t n_seg,
+                                   const int32_t* seg_of, const double* U, const double* ivar, double* W_out) {
+  return guarded(ctx, [&] {
+    prom::RcDev& rc = ctx->rc;
+    PROM_REQUIRE(n_comp >= 1 && n_comp <= prom::kDtMaxComp, "prom_filter_weights_orders: n_comp must lie in [1, 16]");
+    PROM_REQUIRE(n_exp >= 1 && n_pix >= 0 && n_seg >= 1,
+                 "prom_filter_weights_orders: n_exp and n_seg must be >= 1 and n_pix >= 0");
+    const int64_t nu = (int64_t)n_seg * n_exp * n_comp, ni = (int64_t)n_exp * n_pix, nw = ni * n_comp;
+    PROM_REQUIRE(U && (n_pix == 0 || (ivar && W_out && seg_of)),
+                 "prom_filter_weights_orders: U, seg_of, ivar or W_out missing");
+    for (int64_t i = 0; i < nu; ++i) PROM_REQUIRE(obs_finite(U[i]), "prom_filter_weights_orders: U must be finite");
+    for (int32_t p = 0; p < n_pix; ++p)
+      PROM_REQUIRE(seg_of[p] >= 0 && seg_of[p] < n_seg, "prom_filter_weights_orders: seg_of outside [0, n_seg)");
+    if (n_pix == 0) return;
+    const hipStream_t st = ctx->stream;
+    upload(rc.fU, U, nu, st);
+    upload(rc.fivar, ivar, ni, st);
+    upload(rc.fseg, seg_of, (int64_t)n_pix, st);
+    rc.fW.ensure(sizeof(double) * (size_t)nw);
+    prom::launch_filter_weights_orders(st, rc.fU.as<double>(), rc.fivar.as<double>(), rc.fseg.as<int32_t>(),
+                                       rc.fW.as<double>(), n_exp, n_comp, n_pix, nullptr, nullptr);
+    download(W_out, rc.fW, nw, st);
+    PROM_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int32_t prom_detrend_build_orders(prom_ctx* ctx, int32_t n_exp, int32_t n_comp, int32_t n_seg, const double* U,
+                                  double* W_out) {
+  return guarded(ctx, [&] {
+    prom::ExDev& ex = ctx->ex;
+    const hipStream_t st = ctx->stream;
+    const int32_t n_pix = ctx->obs.n_pix;
+    const int64_t nw = (int64_t)n_comp * n_exp * n_pix;
+    detrend_orders_begin(ctx, "prom_detrend_build_orders", n_exp, n_comp, n_seg, U, st);
+    ex.W.ensure(sizeof(double) * (size_t)std::max<int64_t>(nw, 1));
+    prom::launch_filter_weights_orders(st, ex.U.as<double>(), ex.ivar.as<double>(), ex.dt_seg_of.as<int32_t>(),
+                                       ex.W.as<double>(), n_exp, n_comp, n_pix, nullptr, nullptr);
+    if (W_out) download(W_out, ex.W, nw, st);
+    PROM_HIP(hipStreamSynchronize(st));
+    ex.n_comp = n_comp;
+    ex.dt_n_seg = n_seg;
     ex.dt_set = true;
     if (n_pix > 0) {
       ctx->rc.last = 1;
@@ -931,8 +1092,12 @@ int32_t prom_filter_kernel_ms(prom_ctx* ctx, int32_t n_runs, double* ms_out) {
     double* W = built ? ex.W.as<double>() : rc.W.as<double>();
     double sum = 0.0;
     time_launches(ctx, ctx->stream, n_runs, 1, &sum, [&] {
-      prom::launch_filter_weights(ctx->stream, U, ex.ivar.as<double>(), W, ex.n_exp, rc.last_n_comp, ctx->obs.n_pix,
-                                  ctx->ev[0], ctx->ev[1]);
+      if (built && ex.dt_n_seg > 0)   // (a per-order build: its own instantiation)
+        prom::launch_filter_weights_orders(ctx->stream, U, ex.ivar.as<double>(), ex.dt_seg_of.as<int32_t>(), W,
+                                           ex.n_exp, rc.last_n_comp, ctx->obs.n_pix, ctx->ev[0], ctx->ev[1]);
+      else
+        prom::launch_filter_weights(ctx->stream, U, ex.ivar.as<double>(), W, ex.n_exp, rc.last_n_comp, ctx->obs.n_pix,
+                                    ctx->ev[0], ctx->ev[1]);
     });
     ms_out[0] = sum / n_runs;
   });
@@ -1042,8 +1207,11 @@ void grid_check(prom_ctx* ctx, const char* who, const GridList& g) {
 // injections of a sub-batch under the cap, and the launches of a sub-batch that grow with it, before anything runs
 int32_t grid_plan(prom_ctx* ctx, const SyCall& c, int32_t n_inj, bool recover) {
   const prom::ExDev& ex = ctx->ex;
-  const int64_t per = prom::gr_injection_bytes(ex.n_exp, ctx->obs.n_pix, c.n_comp + c.ones, ex.n_tap, recover);
-  const int32_t nb = prom::gr_sub_batch(grid_cap_bytes(), per, n_inj);
+  const int64_t per = c.orders ? prom::os_injection_bytes(ex.n_exp, ctx->obs.n_pix, ex.od_n_seg, ex.od_n_max,
+                                                          c.n_comp + c.ones, ex.n_tap)
+                               : prom::gr_injection_bytes(ex.n_exp, ctx->obs.n_pix, c.n_comp + c.ones, ex.n_tap, recover);
+  const int32_t nb = c.orders ? prom::os_sub_batch(grid_cap_bytes(), per, n_inj, ex.od_n_seg)
+                              : prom::gr_sub_batch(grid_cap_bytes(), per, n_inj);
   if (c.highpass && prom::hp_workgroups((int64_t)nb * ex.n_exp, ex.hp_n_seg) > kMaxGrid)
     throw Error(PROM_E_ARG, "k_highpass: n_inj n_exp n_seg too large for one launch");
   static const bool debug = std::getenv("PROM_DEBUG") != nullptr;
@@ -1059,15 +1227,17 @@ void grid_buffers(prom_ctx* ctx, hipStream_t st, const SyCall& c, const GridList
   prom::SyDev& sy = ctx->sy;
   const prom::ExDev& ex = ctx->ex;
   const int32_t n_exp = sy.n_exp, n_pix = sy.n_pix, n_cols = c.n_comp + c.ones;
-  const size_t B = (size_t)nb, n = (size_t)n_exp * n_pix, work = (size_t)(n_exp * prom::sy_pitch(n_pix));
+  const int32_t width = sy_width(ctx, c);
+  const size_t B = (size_t)nb, n = (size_t)n_exp * n_pix, work = (size_t)(n_exp * prom::sy_pitch(width));
+  const size_t items = B * (size_t)sy_items(ctx, c);   // (per order: an item per order of every injection)
   sy.D.ensure(sizeof(double) * B * n);
   sy.out.ensure(sizeof(double) * B * n);
-  sy.r.ensure(sizeof(double) * B * work);
-  sy.w.ensure(sizeof(double) * B * work);
-  sy.a.ensure(sizeof(double) * B * n_exp);
-  sy.ended.ensure(sizeof(int32_t) * B * prom::kGrFlags);
-  sy.part.ensure(2 * sizeof(double) * B * n_exp * prom::sy_tiles(n_pix));
-  sy.U.ensure(sizeof(double) * B * n_exp * n_cols);
+  sy.r.ensure(sizeof(double) * items * work);
+  sy.w.ensure(sizeof(double) * items * work);
+  sy.a.ensure(sizeof(double) * items * n_exp);
+  sy.ended.ensure(sizeof(int32_t) * items * prom::kGrFlags);
+  sy.part.ensure(2 * sizeof(double) * items * n_exp * prom::sy_tiles(width));
+  sy.U.ensure(sizeof(double) * items * n_exp * n_cols);
   sy.q.ensure(sizeof(double) * (size_t)n_wav);
   sy.Fj.ensure(sizeof(double) * B * n_exp * ex.n_tap);
   sy.model.ensure(sizeof(double) * B * n);
@@ -1101,13 +1271,19 @@ void grid_clean(prom_ctx* ctx, hipStream_t st, const double* wav, const double* 
                            sy.D.as<double>(), n_exp, n_pix, nb);
   if (c.highpass)
     highpass_launch(ex, st, sy.D.as<double>(), (int64_t)nb * n_exp, n_pix);
-  prom::launch_sysrem(st, sy.D.as<double>(), ex.ivar.as<double>(), sy.r.as<double>(), sy.w.as<double>(),
-                      sy.a.as<double>(), sy.ended.as<int32_t>(), sy.part.as<double>(), sy.U.as<double>(),
-                      sy.out.as<double>(), n_exp, n_pix, c.n_comp, c.n_iter, c.ones, nb);
+  if (c.orders)
+    prom::launch_sysrem_orders(st, sy.D.as<double>(), ex.ivar.as<double>(), ex.od_seg.as<int32_t>(),
+                               ex.od_perm.as<int32_t>(), sy.r.as<double>(), sy.w.as<double>(), sy.a.as<double>(),
+                               sy.ended.as<int32_t>(), sy.part.as<double>(), sy.U.as<double>(), sy.out.as<double>(),
+                               n_exp, n_pix, ex.od_n_seg, ex.od_n_max, c.n_comp, c.n_iter, c.ones, nb);
+  else
+    prom::launch_sysrem(st, sy.D.as<double>(), ex.ivar.as<double>(), sy.r.as<double>(), sy.w.as<double>(),
+                        sy.a.as<double>(), sy.ended.as<int32_t>(), sy.part.as<double>(), sy.U.as<double>(),
+                        sy.out.as<double>(), n_exp, n_pix, c.n_comp, c.n_iter, c.ones, nb);
 }
 
 // no pixel: every component of every entry ends at once
-void grid_zero_U(const SyCall& c, int32_t n_exp, int32_t n_inj, double* U_out) {
+void grid_zero_U(const SyCall& c, int32_t n_exp, int64_t n_inj, double* U_out) {
   const int32_t n_cols = c.n_comp + c.ones;
   if (!U_out) return;
   for (int64_t i = 0; i < (int64_t)n_inj * n_exp; ++i)
@@ -1126,8 +1302,8 @@ void inject_grid_on(prom_ctx* ctx, hipStream_t st, const double* wav, const doub
                     const GridList& g, double* U_out, double* cleaned_out, double* injected_out) {
   prom::SyDev& sy = ctx->sy;
   const int32_t n_exp = sy.n_exp, n_pix = sy.n_pix, n_cols = c.n_comp + c.ones;
-  const int64_t n = (int64_t)n_exp * n_pix, nu = (int64_t)n_exp * n_cols;
-  if (n_pix == 0) return grid_zero_U(c, n_exp, g.n_inj, U_out);
+  const int64_t n = (int64_t)n_exp * n_pix, nu = (int64_t)sy_items(ctx, c) * n_exp * n_cols;
+  if (n_pix == 0) return grid_zero_U(c, n_exp, (int64_t)g.n_inj * sy_items(ctx, c), U_out);
   if (g.n_inj == 0 || (!U_out && !cleaned_out && !injected_out)) return;
   const int32_t nb_max = grid_plan(ctx, c, g.n_inj, false);
   grid_forget(ctx);
@@ -1205,8 +1381,8 @@ void recover_grid_on(prom_ctx* ctx, hipStream_t st, const double* wav, const dou
 }
 
 // a SyCall whose trial and scale pass the single calls' checks: the list has its own
-SyCall grid_call(int32_t source, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones) {
-  return SyCall{source, 0, highpass, n_comp, n_iter, ones, 0.0};
+SyCall grid_call(int32_t source, int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones, int32_t orders = 0) {
+  return SyCall{source, 0, highpass, n_comp, n_iter, ones, 0.0, orders};
 }
 
 }  // namespace
@@ -1235,6 +1411,36 @@ int32_t prom_spectrum_inject_grid(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, c
     sysrem_check(ctx, "prom_spectrum_inject_grid", c);
     grid_check(ctx, "prom_spectrum_inject_grid", g);
     const hipStream_t st = sy_spectrum(ctx, "prom_spectrum_inject_grid", n_orb, n_wav, wav, R);
+    inject_grid_on(ctx, st, sy.wav.as<double>(), sy.R.as<double>(), n_wav, c, g, U_out, cleaned_out, injected_out);
+  });
+}
+
+// SYSREM per order over a grid: entry b is what the per-order inject call gives for (trial[b], scale[b]); U_out is
+// [n_inj][n_seg][n_exp][n_comp + ones]
+int32_t prom_transit_inject_grid_orders(prom_ctx* ctx, int32_t n_inj, const int32_t* trial, const double* scale,
+                                        int32_t highpass, int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out,
+                                        double* cleaned_out, double* injected_out) {
+  return guarded(ctx, [&] {
+    const SyCall c = grid_call(2, highpass, n_comp, n_iter, ones, 1);
+    const GridList g{n_inj, trial, scale};
+    sysrem_check(ctx, "prom_transit_inject_grid_orders", c);
+    grid_check(ctx, "prom_transit_inject_grid_orders", g);
+    const TransitArgs t = ex_transit(ctx, "prom_transit_inject_grid_orders");
+    inject_grid_on(ctx, t.st, t.wav, t.R, t.n_wav, c, g, U_out, cleaned_out, injected_out);
+  });
+}
+
+int32_t prom_spectrum_inject_grid_orders(prom_ctx* ctx, int32_t n_orb, int64_t n_wav, const double* wav, const double* R,
+                                         int32_t n_inj, const int32_t* trial, const double* scale, int32_t highpass,
+                                         int32_t n_comp, int32_t n_iter, int32_t ones, double* U_out,
+                                         double* cleaned_out, double* injected_out) {
+  return guarded(ctx, [&] {
+    prom::SyDev& sy = ctx->sy;
+    const SyCall c = grid_call(3, highpass, n_comp, n_iter, ones, 1);
+    const GridList g{n_inj, trial, scale};
+    sysrem_check(ctx, "prom_spectrum_inject_grid_orders", c);
+    grid_check(ctx, "prom_spectrum_inject_grid_orders", g);
+    const hipStream_t st = sy_spectrum(ctx, "prom_spectrum_inject_grid_orders", n_orb, n_wav, wav, R);
     inject_grid_on(ctx, st, sy.wav.as<double>(), sy.R.as<double>(), n_wav, c, g, U_out, cleaned_out, injected_out);
   });
 }

@@ -24,6 +24,7 @@
 // without NaN and U = 0 the eight numbers are prom_spectrum_expose's bit for bit.  No atomics.
 #include "prom_internal.h"
 #include "detrend_index.h"
+#include "order_sysrem_index.h"
 
 namespace prom {
 
@@ -45,6 +46,29 @@ __global__ void __launch_bounds__(kDtBlock) k_detrend(double* __restrict__ model
   double c[NC];
   const bool ok = dt_coefficients<NC>(S, m_stride, W + dt_w(0, 0, p, n_exp, n_pix), n_pix, n_exp, c);
   dt_apply<NC>(S, M, m_stride, U, n_exp, c, ok);
+  flag[dt_flag(j, p, n_pix)] = ok ? 1 : 0;
+}
+
+// The per-order instantiation (a per-order filter resident, prom_detrend_set_orders / prom_detrend_build_orders):
+// k_detrend's text with the U pointer moved per lane by seg_of[p] n_exp NC, the basis of p's own order; W is per pixel
+// already.  U becomes a vector load.  A kernel of its own, so that k_detrend's instantiations are what they were.
+template <int NC, bool OUT>
+__global__ void __launch_bounds__(kDtBlock) k_detrend_orders(double* __restrict__ model, const double* __restrict__ src,
+                                                              const double* __restrict__ U,
+                                                              const double* __restrict__ W,
+                                                              const int32_t* __restrict__ seg_of,
+                                                              uint8_t* __restrict__ flag, int32_t n_exp,
+                                                              int32_t n_trial, int32_t n_pix, int32_t n_tiles) {
+  const int32_t tid = threadIdx.x;
+  const int32_t p = dt_pixel(dt_wg_tile(blockIdx.x, n_tiles), tid);
+  const int32_t j = dt_trial(dt_wg_group(blockIdx.x, n_tiles), tid);
+  if (p >= n_pix || j >= n_trial) return;
+  double* M = model + ex_model(0, j, p, n_trial, n_pix);
+  const double* S = OUT ? src + ex_model(0, j, p, n_trial, n_pix) : M;   // (in place: src is not looked at)
+  const int64_t m_stride = (int64_t)n_trial * n_pix;
+  double c[NC];
+  const bool ok = dt_coefficients<NC>(S, m_stride, W + dt_w(0, 0, p, n_exp, n_pix), n_pix, n_exp, c);
+  dt_apply<NC>(S, M, m_stride, U + fo_u(seg_of[p], n_exp, NC), n_exp, c, ok);
   flag[dt_flag(j, p, n_pix)] = ok ? 1 : 0;
 }
 
@@ -112,7 +136,8 @@ __global__ void __launch_bounds__(kVmBlock) k_model_moments(const double* __rest
 }
 
 void launch_detrend(hipStream_t s, double* model, const double* U, const double* W, uint8_t* flag, int32_t n_exp,
-                    int32_t n_comp, int32_t n_trial, int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1, const double* src) {
+                    int32_t n_comp, int32_t n_trial, int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1, const double* src,
+                    const int32_t* seg_of) {
   if (n_pix <= 0 || n_exp <= 0 || n_trial <= 0) return;
   if (n_comp < 1 || n_comp > kDtMaxComp) throw Error(PROM_E_ARG, "k_detrend: n_comp outside [1, 16]");
   const int64_t wgs = dt_workgroups(n_trial, n_pix);
@@ -123,7 +148,13 @@ void launch_detrend(hipStream_t s, double* model, const double* U, const double*
   switch (n_comp) {
 #define PROM_DT_CASE(NC)                                                                                        \
   case NC:                                                                                                      \
-    if (src && src != model)                                                                                    \
+    if (seg_of && src && src != model)                                                                          \
+      hipLaunchKernelGGL((k_detrend_orders<NC, true>), grid, dim3(kDtBlock), 0, s, model, src, U, W, seg_of,    \
+                         flag, n_exp, n_trial, n_pix, n_tiles);                                                 \
+    else if (seg_of)                                                                                            \
+      hipLaunchKernelGGL((k_detrend_orders<NC, false>), grid, dim3(kDtBlock), 0, s, model, nullptr, U, W,       \
+                         seg_of, flag, n_exp, n_trial, n_pix, n_tiles);                                         \
+    else if (src && src != model)                                                                               \
       hipLaunchKernelGGL((k_detrend<NC, true>), grid, dim3(kDtBlock), 0, s, model, src, U, W, flag, n_exp,      \
                          n_trial, n_pix, n_tiles);                                                              \
     else                                                                                                        \

@@ -461,6 +461,10 @@ struct ExDev {
   int32_t n_comp = 0;
   DevBuf U, W, flag;                      // [n_exp][n_comp], [n_comp][n_exp][n_pix], [n_trial][n_pix] bytes
   bool dt_ran = false;                    // the last call on last_wav / last_R was a detrended one
+  // A per-order filter (prom_detrend_set_orders / prom_detrend_build_orders): U is [dt_n_seg][n_exp][n_comp] and pixel
+  // p takes the basis of order dt_seg_of[p]; 0: one basis.  prom_orders_set drops it.
+  int32_t dt_n_seg = 0;
+  DevBuf dt_seg_of;                       // [n_pix] int32
   // The high-pass of the filtered exposures (prom_highpass_set): like the filter above it lives while the table it
   // was set for does, and prom_expose_set clears hp_set.
   bool hp_set = false;
@@ -474,7 +478,9 @@ struct ExDev {
   // they were set for does, and prom_expose_set clears od_set.
   bool od_set = false;
   int32_t od_n_seg = 0;
+  int32_t od_n_max = 0;                   // the longest order's pixels: the width of a per-order SYSREM item
   DevBuf od_seg, od_perm, od_keep;        // seg_first[n_seg + 1], perm[n_pix] (int32), keep[n_seg] (bytes)
+  std::vector<int32_t> od_seg_host, od_perm_host;   // the host's copies: seg_of of a per-order filter is formed from them
   DevBuf od_rec, od_tot;                  // a batch's records [n_exp][nb][n_seg][8], the totals [n_exp][n_trial][4]
   bool od_ran = false;                    // the last call was a per-order one: its final model and flags are resident
 };
@@ -514,6 +520,7 @@ struct SyDev {
   // the last call, for prom_sysrem_kernel_ms to repeat (source 0: none yet, 1: clean, 2: transit, 3: spectrum)
   int32_t last_source = 0, last_trial = 0, last_highpass = 0, last_n_comp = 0, last_n_iter = 0, last_ones = 0;
   int32_t last_n_orb = 0;
+  int32_t last_orders = 0;                // the last call cleaned per order: r .. U hold [n_seg] items n_max wide
   int64_t last_n_wav = 0;
   double last_scale = 0.0;
 };
@@ -524,6 +531,7 @@ struct RcDev {
   DevBuf W;                               // [n_comp + ones][n_exp][n_pix] ([B][...] in a recovery grid's sub-batch)
   DevBuf model;                           // a recovery grid's filtered model of one injection, [n_exp][n_trial][n_pix]
   DevBuf fU, fivar, fW;                   // prom_filter_weights' copies of the caller's arrays and its W
+  DevBuf fseg;                            // prom_filter_weights_orders' copy of seg_of
   int32_t last = 0;                       // 0: none, 1: prom_detrend_build (ExDev's U, W), 2: a recover call (SyDev's U, W)
   int32_t last_n_comp = 0;
 };
@@ -696,7 +704,8 @@ void launch_expose(hipStream_t s, const double* wav, const double* q, const doub
 // [j_first, j_first + nb) of that model into the batch's partial records, as launch_expose's
 void launch_detrend(hipStream_t s, double* model, const double* U, const double* W, uint8_t* flag, int32_t n_exp,
                     int32_t n_comp, int32_t n_trial, int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1,
-                    const double* src = nullptr);   // (src: out of place, the model is read from src and src stays)
+                    const double* src = nullptr,   // (src: out of place, the model is read from src and src stays)
+                    const int32_t* seg_of = nullptr);   // (seg_of[n_pix]: U is [n_seg][n_exp][n_comp], a basis per order)
 void launch_model_moments(hipStream_t s, const double* model, const uint8_t* flag, const double* data,
                           const double* ivar, int32_t n_pix, int32_t n_exp, int32_t n_trial, int32_t j_first,
                           int32_t nb, double* part, hipEvent_t ev0, hipEvent_t ev1);
@@ -740,9 +749,20 @@ void launch_gather_grid(hipStream_t s, const double* F, double* Fj, const int32_
                         int32_t n_tap, int32_t n_inj);
 void launch_inject_grid(hipStream_t s, const double* raw, const double* model, const double* scale, double* D,
                         int32_t n_exp, int32_t n_pix, int32_t n_inj);
+// SYSREM per order (prom_sysrem.hip, order_sysrem_index.h): launch_sysrem's steps with every order seg_first[n_seg + 1]
+// / perm[n_pix] (on the device) of every injection as a batch item n_max = max n_s wide: r, w, a, part and U are
+// [n_inj][n_seg][the single call's at n_pix = n_max], ended is int32 [n_inj n_seg][kGrFlags], D and out stay
+// [n_inj][n_exp][n_pix]; the same number of launches
+void launch_sysrem_orders(hipStream_t s, const double* D, const double* ivar, const int32_t* seg_first,
+                          const int32_t* perm, double* r, double* w, double* a, int32_t* ended, double* part, double* U,
+                          double* out, int32_t n_exp, int32_t n_pix, int32_t n_seg, int32_t n_max, int32_t n_comp,
+                          int32_t n_iter, int32_t ones, int32_t n_inj = 1);
 // the filter's weights (prom_filter.hip): W[n_comp][n_exp][n_pix] of U[n_exp][n_comp] and ivar[n_exp][n_pix]
 void launch_filter_weights(hipStream_t s, const double* U, const double* ivar, double* W, int32_t n_exp, int32_t n_comp,
                            int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1, int32_t n_inj = 1);   // (U, W: [n_inj][...])
+// ... and per order: U[n_seg][n_exp][n_comp], pixel p takes the basis of order seg_of[p] (on the device)
+void launch_filter_weights_orders(hipStream_t s, const double* U, const double* ivar, const int32_t* seg_of, double* W,
+                                  int32_t n_exp, int32_t n_comp, int32_t n_pix, hipEvent_t ev0, hipEvent_t ev1);
 // Star.getFstarIntegrated with rotation: the disk-integrated stellar flux per wavelength (prom_fn.hip)
 void launch_star_disk(hipStream_t s, const SigTabDev& tb, const double* shift, const double* clv, const double* rho,
                       int32_t n_cells, double dphi, double drho, const double* wav, int64_t n_wav, double* out);

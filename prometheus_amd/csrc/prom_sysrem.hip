@@ -27,9 +27,17 @@
 // `col` of b's own row of `ended`, so it stops b's later launches and nobody else's.  Two kernels are the grid's own:
 //   k_gather_grid    Fj[e][b][tap] = F[e][trial[b]][tap]: k_expose then runs unchanged with B in n_trial's place
 //   k_inject_grid    D[b][e][p] from raw[e][p], model[e][b][p] and scale[b]
+//
+// SYSREM per order (prom_sysrem_clean_orders, prom_*_inject_orders, prom_*_inject_grid_orders): an order is one more
+// batch item.  Item y = b n_seg + s of the work buffers is order s of injection b, n_max = max n_s wide
+// (order_sysrem_index.h); k_sysrem_fill, k_sysrem_step and k_sysrem_rows run unchanged over n_inj n_seg items.
+//   k_sysrem_prep_orders    w and r of item y from D[b][e][perm[first_s + i]], the padding beyond n_s as above
+//   k_sysrem_finish_orders  cleaned[b][e][perm[first_s + i]] of item y; perm is a permutation, so every entry of the
+//                           cleaned data is written exactly once
 #include "prom_internal.h"
 #include "sysrem_index.h"
 #include "grid_index.h"
+#include "order_sysrem_index.h"
 
 namespace prom {
 
@@ -248,6 +256,42 @@ __global__ void __launch_bounds__(kSyFlatBlock) k_sysrem_finish(const double* __
   out[ex_data(e, p, n_pix)] = w[at] > 0.0 ? r[at] : D[ex_data(e, p, n_pix)];
 }
 
+__global__ void __launch_bounds__(kSyFlatBlock) k_sysrem_prep_orders(
+    const double* __restrict__ D, const double* __restrict__ ivar, const int32_t* __restrict__ seg_first,
+    const int32_t* __restrict__ perm, double* __restrict__ r, double* __restrict__ w, int32_t n_exp, int32_t n_pix,
+    int32_t n_seg, int64_t pitch) {
+  const int64_t t = (int64_t)blockIdx.x * kSyFlatBlock + threadIdx.x;
+  if (t >= (int64_t)n_exp * pitch) return;
+  const int32_t y = blockIdx.y;   // the item: order s of injection b
+  const int32_t b = os_item_injection(y, n_seg), s = os_item_order(y, n_seg);
+  const int32_t e = (int32_t)(t / pitch), i = (int32_t)(t % pitch);
+  const int32_t n_s = seg_first[s + 1] - seg_first[s];
+  double wv = 0.0, rv = 0.0;
+  if (i < n_s) {
+    const int32_t p = perm[os_slot(seg_first, s, i)];
+    const double d = D[os_data(b, e, p, n_exp, n_pix)];
+    wv = sy_weight(ivar[ex_data(e, p, n_pix)], d);
+    if (wv > 0.0) rv = d;
+  }
+  w[os_work(y, e, i, n_exp, pitch)] = wv;
+  r[os_work(y, e, i, n_exp, pitch)] = rv;
+}
+
+__global__ void __launch_bounds__(kSyFlatBlock) k_sysrem_finish_orders(
+    const double* __restrict__ D, const double* __restrict__ r, const double* __restrict__ w,
+    const int32_t* __restrict__ seg_first, const int32_t* __restrict__ perm, double* __restrict__ out, int32_t n_exp,
+    int32_t n_pix, int32_t n_seg, int32_t n_max, int64_t pitch) {
+  const int64_t t = (int64_t)blockIdx.x * kSyFlatBlock + threadIdx.x;
+  if (t >= (int64_t)n_exp * n_max) return;
+  const int32_t y = blockIdx.y;
+  const int32_t b = os_item_injection(y, n_seg), s = os_item_order(y, n_seg);
+  const int32_t e = (int32_t)(t / n_max), i = (int32_t)(t % n_max);
+  if (i >= seg_first[s + 1] - seg_first[s]) return;
+  const int32_t p = perm[os_slot(seg_first, s, i)];
+  const int64_t at = os_work(y, e, i, n_exp, pitch), da = os_data(b, e, p, n_exp, n_pix);
+  out[da] = w[at] > 0.0 ? r[at] : D[da];
+}
+
 static uint32_t flat_grid(int64_t n, const char* who) {
   const int64_t wgs = sy_flat_workgroups(n);
   if (wgs > (((int64_t)1 << 31) - 1)) throw Error(PROM_E_ARG, std::string(who) + ": too many entries for one launch");
@@ -284,20 +328,15 @@ void launch_inject_grid(hipStream_t s, const double* raw, const double* model, c
   PROM_HIP(hipGetLastError());
 }
 
-void launch_sysrem(hipStream_t s, const double* D, const double* ivar, double* r, double* w, double* a, int32_t* ended,
-                   double* part, double* U, double* out, int32_t n_exp, int32_t n_pix, int32_t n_comp, int32_t n_iter,
-                   int32_t ones, int32_t n_inj) {
-  if (n_pix <= 0 || n_exp <= 0 || n_inj <= 0) return;
-  if (n_exp > kSyMaxExp) throw Error(PROM_E_ARG, "k_sysrem_rows: n_exp above 4096");
-  if (n_inj > kGrMaxBatch) throw Error(PROM_E_ARG, "k_sysrem_step: more than 65535 injections in one launch");
+// the components of `items` batch items n_pix wide, between the prep and the finish kernel: the column of ones, then
+// per component the first a, n_iter steps and row sums, and the subtraction
+static void sysrem_components(hipStream_t s, double* r, double* w, double* a, int32_t* ended, double2* pt, double* U,
+                              int32_t n_exp, int32_t n_pix, int32_t n_comp, int32_t n_iter, int32_t ones,
+                              int32_t items) {
   const int32_t n_cols = n_comp + ones, n_tiles = sy_tiles(n_pix);
   const int64_t pitch = sy_pitch(n_pix);
-  const uint32_t B = (uint32_t)n_inj;   // the injection is blockIdx.y (blockIdx.x of the one-workgroup k_sysrem_rows)
+  const uint32_t B = (uint32_t)items;   // the item is blockIdx.y (blockIdx.x of the one-workgroup k_sysrem_rows)
   const dim3 fill_grid((uint32_t)sy_flat_workgroups(n_exp), B), tiles((uint32_t)n_tiles, B);
-  double2* pt = reinterpret_cast<double2*>(part);
-  PROM_HIP(hipMemsetAsync(ended, 0, sizeof(int32_t) * kGrFlags * (size_t)n_inj, s));
-  hipLaunchKernelGGL(k_sysrem_prep, dim3(flat_grid((int64_t)n_exp * pitch, "k_sysrem_prep"), B), dim3(kSyFlatBlock), 0,
-                     s, D, ivar, r, w, n_exp, n_pix, pitch);
   int32_t col = 0;
   if (ones) {
     hipLaunchKernelGGL(k_sysrem_fill, fill_grid, dim3(kSyFlatBlock), 0, s, a, U, n_exp, col, n_cols, 1.0);
@@ -316,8 +355,42 @@ void launch_sysrem(hipStream_t s, const double* D, const double* ivar, double* r
     hipLaunchKernelGGL((k_sysrem_step<true>), tiles, dim3(kSyBlock), 0, s, r, w, a, ended + col, pt, n_exp, pitch,
                        n_tiles);
   }
+}
+
+void launch_sysrem(hipStream_t s, const double* D, const double* ivar, double* r, double* w, double* a, int32_t* ended,
+                   double* part, double* U, double* out, int32_t n_exp, int32_t n_pix, int32_t n_comp, int32_t n_iter,
+                   int32_t ones, int32_t n_inj) {
+  if (n_pix <= 0 || n_exp <= 0 || n_inj <= 0) return;
+  if (n_exp > kSyMaxExp) throw Error(PROM_E_ARG, "k_sysrem_rows: n_exp above 4096");
+  if (n_inj > kGrMaxBatch) throw Error(PROM_E_ARG, "k_sysrem_step: more than 65535 injections in one launch");
+  const int64_t pitch = sy_pitch(n_pix);
+  const uint32_t B = (uint32_t)n_inj;   // the injection is blockIdx.y
+  PROM_HIP(hipMemsetAsync(ended, 0, sizeof(int32_t) * kGrFlags * (size_t)n_inj, s));
+  hipLaunchKernelGGL(k_sysrem_prep, dim3(flat_grid((int64_t)n_exp * pitch, "k_sysrem_prep"), B), dim3(kSyFlatBlock), 0,
+                     s, D, ivar, r, w, n_exp, n_pix, pitch);
+  sysrem_components(s, r, w, a, ended, reinterpret_cast<double2*>(part), U, n_exp, n_pix, n_comp, n_iter, ones, n_inj);
   hipLaunchKernelGGL(k_sysrem_finish, dim3(flat_grid((int64_t)n_exp * n_pix, "k_sysrem_finish"), B),
                      dim3(kSyFlatBlock), 0, s, D, r, w, out, n_exp, n_pix, pitch);
+  PROM_HIP(hipGetLastError());
+}
+
+void launch_sysrem_orders(hipStream_t s, const double* D, const double* ivar, const int32_t* seg_first,
+                          const int32_t* perm, double* r, double* w, double* a, int32_t* ended, double* part, double* U,
+                          double* out, int32_t n_exp, int32_t n_pix, int32_t n_seg, int32_t n_max, int32_t n_comp,
+                          int32_t n_iter, int32_t ones, int32_t n_inj) {
+  if (n_pix <= 0 || n_exp <= 0 || n_inj <= 0 || n_seg <= 0 || n_max <= 0) return;
+  if (n_exp > kSyMaxExp) throw Error(PROM_E_ARG, "k_sysrem_rows: n_exp above 4096");
+  if ((int64_t)n_inj * n_seg > kGrMaxBatch)
+    throw Error(PROM_E_ARG, "k_sysrem_step: more than 65535 (injection, order) items in one launch");
+  const int64_t pitch = sy_pitch(n_max);
+  const int32_t items = n_inj * n_seg;
+  const uint32_t B = (uint32_t)items;   // the item y = b n_seg + s is blockIdx.y
+  PROM_HIP(hipMemsetAsync(ended, 0, sizeof(int32_t) * kGrFlags * (size_t)items, s));
+  hipLaunchKernelGGL(k_sysrem_prep_orders, dim3(flat_grid((int64_t)n_exp * pitch, "k_sysrem_prep_orders"), B),
+                     dim3(kSyFlatBlock), 0, s, D, ivar, seg_first, perm, r, w, n_exp, n_pix, n_seg, pitch);
+  sysrem_components(s, r, w, a, ended, reinterpret_cast<double2*>(part), U, n_exp, n_max, n_comp, n_iter, ones, items);
+  hipLaunchKernelGGL(k_sysrem_finish_orders, dim3(flat_grid((int64_t)n_exp * n_max, "k_sysrem_finish_orders"), B),
+                     dim3(kSyFlatBlock), 0, s, D, r, w, seg_first, perm, out, n_exp, n_pix, n_seg, n_max, pitch);
   PROM_HIP(hipGetLastError());
 }
 

@@ -700,8 +700,17 @@ class _ExposeJob:
         self.obs.upload(dev)
         if dev.expose_key != self.ex.key:
             dev.expose_set(self.ex.rows, self.ex.weights, self.ex.factors, self.ex.data, self.ex.ivar, key=self.ex.key)
+        per_order = self.dt is not None and self.dt.orders is not None
+        if per_order:   # (a per-order filter is set for the resident orders, and new orders drop it: they go first)
+            od = self.od if self.od is not None else self.dt.orders
+            if dev.orders_key != od.key:
+                dev.orders_set(od.seg_first, od.perm, od.keep, key=od.key)
         if self.dt is not None and dev.detrend_key != self.dt.key:   # (a new table has dropped the filter)
-            if self.dt.on_device:
+            if per_order and self.dt.on_device:
+                dev.detrend_build_orders(self.dt.U, key=self.dt.key)
+            elif per_order:
+                dev.detrend_set_orders(self.dt.U, self.dt.W, key=self.dt.key)
+            elif self.dt.on_device:
                 dev.detrend_build(self.dt.U, key=self.dt.key)
             else:
                 dev.detrend_set(self.dt.U, self.dt.W, key=self.dt.key)
@@ -740,9 +749,10 @@ class _InjectJob:
     the (one) chunk's R."""
 
     def __init__(self, inj, n_orb, trial, scale, n_comp, n_iter, ones, highpass=None, broaden=None,
-                 want_injected=False):
+                 want_injected=False, sysrem_orders=None):
         self.inj = inj
-        self.table = _ExposeJob(inj.exposures, n_orb, False, highpass=highpass, broaden=broaden)
+        self.table = _ExposeJob(inj.exposures, n_orb, False, highpass=highpass, orders=sysrem_orders, broaden=broaden)
+        self.per_order = sysrem_orders is not None   # (SYSREM per order: the orders go up with the table)
         self.br = broaden
         self.args = dict(n_comp=n_comp, n_iter=n_iter, ones=ones, highpass=highpass is not None,
                          injected=want_injected)
@@ -756,14 +766,15 @@ class _InjectJob:
             dev.sysrem_set(self.inj.raw, key=self.inj.key)
 
     def clean(self, dev):
-        self.add(dev.sysrem_clean(**self.args))
+        self.add((dev.sysrem_clean_orders if self.per_order else dev.sysrem_clean)(**self.args))
 
     def run(self, dev, wavelength, a: int, b: int):
         if not self.whole:   # (inject refuses such a run before it starts)
             raise RuntimeError("inject: the run was split into wavelength shards or chunks")
         if self.br is not None:
             dev.transit_broaden()
-        return dev.transit_inject(self.trial, self.scale, **self.args)
+        call = dev.transit_inject_orders if self.per_order else dev.transit_inject
+        return call(self.trial, self.scale, **self.args)
 
     def add(self, part) -> None:
         self.U, self.data, self.injected = part
@@ -808,8 +819,9 @@ class _RecoverJob:
 class _InjectGridJob(_InjectJob):
     """One Transit.inject_grid call: what _InjectJob uploads, then every injection of the list in one call."""
 
-    def __init__(self, inj, n_orb, trials, scales, n_comp, n_iter, ones, highpass=None, broaden=None, want_data=True):
-        super().__init__(inj, n_orb, 0, 0.0, n_comp, n_iter, ones, highpass, broaden)
+    def __init__(self, inj, n_orb, trials, scales, n_comp, n_iter, ones, highpass=None, broaden=None, want_data=True,
+                 sysrem_orders=None):
+        super().__init__(inj, n_orb, 0, 0.0, n_comp, n_iter, ones, highpass, broaden, sysrem_orders=sysrem_orders)
         self.args = dict(n_comp=n_comp, n_iter=n_iter, ones=ones, highpass=highpass is not None, data=want_data)
         self.trials, self.scales = trials, scales
 
@@ -818,7 +830,8 @@ class _InjectGridJob(_InjectJob):
             raise RuntimeError("inject_grid: the run was split into wavelength shards or chunks")
         if self.br is not None:
             dev.transit_broaden()
-        return dev.transit_inject_grid(self.trials, self.scales, **self.args)
+        call = dev.transit_inject_grid_orders if self.per_order else dev.transit_inject_grid
+        return call(self.trials, self.scales, **self.args)
 
     def result(self):
         from . import observation as obs
@@ -1212,6 +1225,11 @@ class Transit:
                 raise TypeError("expose: orders must be an observation.Orders")
             if orders.exposures_key != exposures.key:
                 raise ValueError("expose: the Orders were made for other exposures (another table, pixels or data)")
+            if detrend is not None and detrend.orders is not None and not (
+                    np.array_equal(orders.seg_first, detrend.orders.seg_first)
+                    and np.array_equal(orders.perm, detrend.orders.perm)):
+                raise ValueError("expose: orders= and the per-order Detrend's Orders must cut the pixels alike (the "
+                                 "device keeps one set of orders; keep may differ)")
         n_orb = len(self.spatialGrid.constructOrbphaseAxis())
         if int(exposures.rows.max()) >= n_orb or int(exposures.rows.min()) < 0:
             raise ValueError("expose: a tap reads row %d, the transit has %d phases"
@@ -1239,7 +1257,7 @@ class Transit:
         return vm
 
     def clean(self, inj, n_comp: int, n_iter: int = 30, ones: bool = False, highpass=None,
-              devices: Optional[Sequence[int]] = None, return_injected: bool = False):
+              devices: Optional[Sequence[int]] = None, return_injected: bool = False, sysrem_orders=None):
         """SYSREM of raw exposures on the device, without a model: ``inj`` is an observation.Injection (the raw data
         of its exposures).  With ``highpass`` (an observation.HighPass made for the same exposures) the data first go
         through the high-pass along each order, as observation.high_pass filters them; then ``n_comp`` components of
@@ -1247,15 +1265,19 @@ class Transit:
         mean first, and a leading column of ones in U), with the exposures' inverse variances as weights
         (include/prom_hip.h, "injection and SYSREM on the device").  Returns an observation.Cleaned: ``U`` for
         observation.Detrend, ``data`` for observation.Exposures, in the caller's pixel order; with
-        ``return_injected`` also ``injected``, the data before SYSREM.  No transit is run.  One device.  TypeError /
-        ValueError for bad arguments, before a device is touched."""
+        ``return_injected`` also ``injected``, the data before SYSREM.  With ``sysrem_orders`` (an observation.Orders
+        made for the same exposures) every echelle order is cleaned on its own in the launches of one call
+        (include/prom_hip.h, "SYSREM per order on the device"): ``U`` is then [n_ord][n_exp][n_comp + ones], in the
+        Orders' order of labels, and a pixel's cleaned data come from its own order.  No transit is run.  One device.
+        TypeError / ValueError for bad arguments, before a device is touched."""
         from . import observation as obs
-        n_comp, n_iter, ones = obs._check_sysrem_args("clean", inj, n_comp, n_iter, ones, highpass)
+        n_comp, n_iter, ones = obs._check_sysrem_args("clean", inj, n_comp, n_iter, ones, highpass, sysrem_orders)
         devices = [0] if devices is None else list(devices)
         if len(devices) != 1:
             raise ValueError("clean: SYSREM runs on one device (%d given)" % len(devices))
         n_orb = len(self.spatialGrid.constructOrbphaseAxis())
-        job = _InjectJob(inj, n_orb, 0, 0.0, n_comp, n_iter, ones, highpass, None, bool(return_injected))
+        job = _InjectJob(inj, n_orb, 0, 0.0, n_comp, n_iter, ones, highpass, None, bool(return_injected),
+                         sysrem_orders)
         dev = _native.get_device(devices[0])
         with dev.lock:
             job.upload(dev)
@@ -1265,16 +1287,17 @@ class Transit:
     def inject(self, inj, trial: int, scale: float = 1.0, n_comp: int = 6, n_iter: int = 30, ones: bool = False,
                highpass=None, broaden=None, return_injected: bool = False,
                devices: Optional[Sequence[int]] = None, max_memory_gb: Optional[float] = None,
-               cull_tau: float = 0.0, options: int = 0):
+               cull_tau: float = 0.0, options: int = 0, sysrem_orders=None):
         """Run the transit, multiply the model of trial ``trial`` of the exposures' table into the raw exposures of
         ``inj`` (an observation.Injection) at strength ``scale``, D = raw (1 + scale (M - 1)) with M the exposures'
         unfiltered model as Transit.expose(return_model=True) gives it (a pixel the model does not cover keeps raw),
         and clean the result as Transit.clean does, all on the device: the injection-recovery step of a detection.
         ``broaden``: the model is formed from R convolved with that observation.Broadening, as in Transit.expose.
-        Returns an observation.Cleaned.  The run must be one wavelength shard on one device in one chunk, as for
-        Transit.expose.  TypeError / ValueError for bad arguments, before a device is touched."""
+        ``sysrem_orders``: SYSREM per echelle order, as in Transit.clean.  Returns an observation.Cleaned.  The run
+        must be one wavelength shard on one device in one chunk, as for Transit.expose.  TypeError / ValueError for
+        bad arguments, before a device is touched."""
         from . import observation as obs
-        n_comp, n_iter, ones = obs._check_sysrem_args("inject", inj, n_comp, n_iter, ones, highpass)
+        n_comp, n_iter, ones = obs._check_sysrem_args("inject", inj, n_comp, n_iter, ones, highpass, sysrem_orders)
         if broaden is not None and not isinstance(broaden, obs.Broadening):
             raise TypeError("inject: broaden must be an observation.Broadening")
         if isinstance(trial, bool) or not isinstance(trial, (int, np.integer)):
@@ -1303,7 +1326,7 @@ class Transit:
                 "has %d); a tap's model M = num / den needs the sums of the whole grid.  Give one device and raise "
                 "max_memory_gb until the grid fits one chunk." % (len(devices), chunk, n_wav))
         job = _InjectJob(inj, n_orb, int(trial), scale, n_comp, n_iter, ones, highpass, broaden,
-                         bool(return_injected))
+                         bool(return_injected), sysrem_orders)
         self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
         return job.result()
 
@@ -1367,11 +1390,11 @@ class Transit:
         return vm
 
     def _grid_checks(self, who, inj, trials, scales, n_comp, n_iter, ones, highpass, broaden, orders, devices,
-                     max_memory_gb):
+                     max_memory_gb, sysrem_orders=None):
         """The refusals of inject_grid / recover_grid, all before a device is touched: (trials, scales, n_comp, n_iter,
         ones, n_orb, devices, max_memory_gb) as the jobs take them."""
         from . import observation as obs
-        n_comp, n_iter, ones = obs._check_sysrem_args(who, inj, n_comp, n_iter, ones, highpass)
+        n_comp, n_iter, ones = obs._check_sysrem_args(who, inj, n_comp, n_iter, ones, highpass, sysrem_orders)
         if broaden is not None and not isinstance(broaden, obs.Broadening):
             raise TypeError("%s: broaden must be an observation.Broadening" % who)
         if orders is not None:
@@ -1399,16 +1422,20 @@ class Transit:
 
     def inject_grid(self, inj, trials, scales, n_comp: int = 6, n_iter: int = 30, ones: bool = False, highpass=None,
                     broaden=None, data: bool = True, devices: Optional[Sequence[int]] = None,
-                    max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0):
+                    max_memory_gb: Optional[float] = None, cull_tau: float = 0.0, options: int = 0,
+                    sysrem_orders=None):
         """A grid of injections cleaned in one call on the device: entry b is what Transit.inject returns for
         (trials[b], scales[b]) with the same other arguments, bit for bit (include/prom_hip.h, "injection grids on
         the device"); the injections share every kernel launch.  ``trials`` and ``scales`` are two lists of one
         length (a scalar is broadcast; observation.injection_grid gives a cross product).  Returns an
-        observation.CleanedGrid; with ``data=False`` only the bases U come back.  One device and one chunk, as for
-        inject.  TypeError / ValueError for bad arguments, before a device is touched."""
+        observation.CleanedGrid; with ``data=False`` only the bases U come back.  ``sysrem_orders``: SYSREM per
+        echelle order, as in Transit.clean; U is then [n_inj][n_ord][n_exp][n_comp + ones].  One device and one chunk,
+        as for inject.  TypeError / ValueError for bad arguments, before a device is touched."""
         trials, scales, n_comp, n_iter, ones, n_orb, devices, max_memory_gb = self._grid_checks(
-            "inject_grid", inj, trials, scales, n_comp, n_iter, ones, highpass, broaden, None, devices, max_memory_gb)
-        job = _InjectGridJob(inj, n_orb, trials, scales, n_comp, n_iter, ones, highpass, broaden, bool(data))
+            "inject_grid", inj, trials, scales, n_comp, n_iter, ones, highpass, broaden, None, devices, max_memory_gb,
+            sysrem_orders)
+        job = _InjectGridJob(inj, n_orb, trials, scales, n_comp, n_iter, ones, highpass, broaden, bool(data),
+                             sysrem_orders)
         self._integrate(max_memory_gb, devices, cull_tau, options, None, want_R=False, observe=job)
         return job.result()
 

@@ -164,7 +164,7 @@ def _weights_of(data, err):
         return np.where(ok, d, 0.0), np.where(ok, 1.0 / (e * e), 0.0)
 
 
-def sysrem(data, err, n_comp: int, n_iter: int = 30, ones: bool = False):
+def sysrem(data, err, n_comp: int, n_iter: int = 30, ones: bool = False, orders=None):
     """SYSREM (Tamuz, Mazeh & Zucker 2005) on the host, once per data set: ``n_comp`` times the weighted rank-one fit
     a[e] c[p] that minimises sum (r - a c)^2 / err^2 over the residuals r is found by ``n_iter`` alternating
     least-squares steps (c from a, then a from c; a starts at ones and is scaled to unit length, the scale going to
@@ -172,10 +172,26 @@ def sysrem(data, err, n_comp: int, n_iter: int = 30, ones: bool = False):
     non-finite data or err, or err <= 0, has no weight.  Returns (U [n_exp][n_comp], the cleaned data, masked entries
     as they came).  With ``ones`` every pixel's weighted mean over the exposures is removed first and U gets a leading
     column of ones for it: U is then [n_exp][n_comp + 1].  U is the basis the model must be filtered with
-    (filter_weights, Detrend)."""
+    (filter_weights, Detrend).  With ``orders`` (an integer label per pixel, as for Orders) every echelle order is
+    cleaned on its own, as every published analysis does: the call is a loop of itself over the orders' columns in
+    ascending label order, U is [n_ord][n_exp][n_comp + ones] and every pixel's cleaned data come from its own
+    order."""
     d0 = np.asarray(data, dtype=np.float64)
     if d0.ndim != 2 or d0.shape[0] < 1:
         raise ValueError("sysrem: data must be [n_exp][n_pix]")
+    if orders is not None:
+        members = _order_members(orders, d0.shape[1], "sysrem")
+        try:
+            e0 = np.broadcast_to(np.asarray(err, dtype=np.float64), d0.shape)
+        except ValueError:
+            raise ValueError("sysrem: err must broadcast to data") from None
+        cleaned = np.array(d0)
+        Us = []
+        for idx in members:
+            U, cl = sysrem(d0[:, idx], e0[:, idx], n_comp, n_iter, ones)
+            Us.append(U)
+            cleaned[:, idx] = cl
+        return np.ascontiguousarray(np.stack(Us)), cleaned
     n_comp, n_iter = int(n_comp), int(n_iter)
     if n_comp < 0 or n_iter < 1 or n_comp + bool(ones) < 1:
         raise ValueError("sysrem: n_comp >= 1 (0 with ones) and n_iter >= 1")
@@ -209,15 +225,28 @@ def sysrem(data, err, n_comp: int, n_iter: int = 30, ones: bool = False):
     return np.ascontiguousarray(np.stack(cols, axis=1)), np.where(iv > 0, r, d0)
 
 
-def filter_weights(U, ivar) -> np.ndarray:
+def filter_weights(U, ivar, orders=None) -> np.ndarray:
     """W[n_comp][n_exp][n_pix] of the basis U[n_exp][n_comp] under the inverse variances ivar[n_exp][n_pix]: at pixel
     p, W_p = (U^T L_p U)^-1 U^T L_p with L_p = diag(ivar[:, p]), the weighted least-squares pseudo-inverse, so that
     m' = m - U (W_p m) removes from a column m what a fit of the basis finds in it.  Entries with ivar = 0 (or not
     finite, or < 0) are exactly 0.  A pixel whose normal matrix U^T L_p U is singular (its smallest eigenvalue not
     above n_comp 2^-52 times its largest: too few weighted exposures, or dependent columns) gets W = 0: it is then
-    filtered by nothing and stays usable."""
+    filtered by nothing and stays usable.  With ``orders`` (an integer label per pixel, as for Orders) U is
+    [n_ord][n_exp][n_comp], a basis per order in ascending label order, and a pixel's W is formed with its own order's
+    basis: a loop of this function over the orders' columns."""
     U = np.asarray(U, dtype=np.float64)
     iv = np.asarray(ivar, dtype=np.float64)
+    if orders is not None:
+        if iv.ndim != 2:
+            raise ValueError("filter_weights: ivar must be [n_exp][n_pix]")
+        members = _order_members(orders, iv.shape[1], "filter_weights")
+        if U.ndim != 3 or U.shape[0] != len(members) or U.shape[2] < 1 or U.shape[1] != iv.shape[0]:
+            raise ValueError("filter_weights: with orders U must be [n_ord][n_exp][n_comp] = [%d][%d][n_comp]"
+                             % (len(members), iv.shape[0]))
+        W = np.zeros((U.shape[2], iv.shape[0], iv.shape[1]))
+        for s, idx in enumerate(members):
+            W[:, :, idx] = filter_weights(U[s], iv[:, idx])
+        return W
     if U.ndim != 2 or U.shape[1] < 1 or iv.ndim != 2 or iv.shape[0] != U.shape[0]:
         raise ValueError("filter_weights: U must be [n_exp][n_comp] and ivar [n_exp][n_pix]")
     if not np.all(np.isfinite(U)):
@@ -249,14 +278,22 @@ class Detrend:
     With ``on_device`` no W is formed or kept on the host (``W`` is then None, and giving one is a ValueError): the
     device forms it from U and the exposures' inverse variances when the filter is uploaded (include/prom_hip.h, "the
     filter's weights on the device"; a Cholesky rule of the device's own, which agrees with filter_weights to
-    rounding on pixels that are not borderline), and the key is made of the exposures' key and U's fingerprint."""
+    rounding on pixels that are not borderline), and the key is made of the exposures' key and U's fingerprint.
+
+    With ``orders`` (an observation.Orders made for the same exposures) the filter has a basis per echelle order, as
+    Transit.clean(sysrem_orders=...) returns it: ``U`` is [n_ord][n_exp][n_comp] in the Orders' order of labels, and
+    every pixel is filtered with the basis of its own order (include/prom_hip.h, "SYSREM per order on the device").
+    ``W`` keeps its shape; None forms it with filter_weights(orders=...), or on the device with ``on_device``."""
 
     MAX_COMP = 16
 
-    def __init__(self, exposures: Exposures, U, W=None, on_device: bool = False):
+    def __init__(self, exposures: Exposures, U, W=None, on_device: bool = False, orders=None):
         from .gasProperties import _content_fingerprint
         if not isinstance(exposures, Exposures):
             raise TypeError("Detrend: exposures must be an observation.Exposures")
+        self.orders = orders
+        if orders is not None:
+            return self._init_per_order(exposures, U, W, bool(on_device), orders)
         u = np.array(U, dtype=np.float64)
         if u.ndim != 2 or u.shape[0] != exposures.n_exp:
             raise ValueError("Detrend: U must be [n_exp][n_comp] with n_exp = %d" % exposures.n_exp)
@@ -286,6 +323,47 @@ class Detrend:
             raise ValueError("Detrend: W must be finite")
         self.W = np.ascontiguousarray(w)                        # what the device sees
         self.key = ("detrend", exposures.key) + _content_fingerprint(self.U, self.W)
+
+    def _init_per_order(self, exposures, U, W, on_device, orders):
+        from .gasProperties import _content_fingerprint
+        if not isinstance(orders, Orders):
+            raise TypeError("Detrend: orders must be an observation.Orders")
+        if orders.exposures_key != exposures.key:
+            raise ValueError("Detrend: the Orders were made for other exposures (another table, pixels or data)")
+        u = np.array(U, dtype=np.float64)
+        if u.ndim != 3 or u.shape[:2] != (orders.n_seg, exposures.n_exp):
+            raise ValueError("Detrend: with orders U must be [n_ord][n_exp][n_comp] = [%d][%d][n_comp]"
+                             % (orders.n_seg, exposures.n_exp))
+        if not 1 <= u.shape[2] <= self.MAX_COMP:
+            raise ValueError("Detrend: n_comp must lie in [1, %d]" % self.MAX_COMP)
+        if not np.all(np.isfinite(u)):
+            raise ValueError("Detrend: U must be finite")
+        self.U = np.ascontiguousarray(u)
+        _, self.n_exp, self.n_comp = self.U.shape
+        self.on_device = on_device
+        self.exposures_key = exposures.key
+        n_pix = exposures.instrument.n_pix
+        self.seg_of = np.zeros(n_pix, dtype=np.int32)           # the order of every device pixel
+        for s in range(orders.n_seg):
+            self.seg_of[orders.perm[orders.seg_first[s]:orders.seg_first[s + 1]]] = s
+        if on_device:
+            if W is not None:
+                raise ValueError("Detrend: on_device forms W on the device; give no W")
+            self.W = None
+            self.key = ("detrend per order on device", orders.key) + _content_fingerprint(self.U)
+            return
+        shape = (self.n_comp, self.n_exp, n_pix)
+        if W is None:
+            w = filter_weights(self.U, exposures.ivar, orders=self.seg_of)   # (ivar and seg_of: the device's order)
+        else:
+            w = np.asarray(W, dtype=np.float64)
+            if w.shape != shape:
+                raise ValueError("Detrend: W must be [n_comp][n_exp][n_pix] = [%d][%d][%d]" % shape)
+            w = exposures.instrument.sort(w)
+        if not np.all(np.isfinite(w)):
+            raise ValueError("Detrend: W must be finite")
+        self.W = np.ascontiguousarray(w)
+        self.key = ("detrend per order", orders.key) + _content_fingerprint(self.U, self.W)
 
 
 MAX_HALF_WIDTH = 512   # of a high-pass' taps (the device's rolling window)
@@ -551,7 +629,7 @@ class Injection:
 
 class Cleaned:
     """What Transit.clean / Transit.inject return: ``U`` [n_exp][n_comp + ones], the basis SYSREM found (the input of
-    Detrend), ``data`` [n_exp][n_pix], the cleaned exposures in the caller's pixel order (the input of Exposures;
+    Detrend; with ``sysrem_orders`` [n_ord][n_exp][n_comp + ones], a basis per echelle order), ``data`` [n_exp][n_pix], the cleaned exposures in the caller's pixel order (the input of Exposures;
     entries without weight as they came), and ``injected`` (None unless asked for): the data after the injection and
     the high-pass, before SYSREM."""
 
@@ -560,7 +638,8 @@ class Cleaned:
 
 
 class CleanedGrid:
-    """What Transit.inject_grid returns: ``trials`` and ``scales`` [n_inj], ``U`` [n_inj][n_exp][n_comp + ones] and
+    """What Transit.inject_grid returns: ``trials`` and ``scales`` [n_inj], ``U`` [n_inj][n_exp][n_comp + ones]
+    ([n_inj][n_ord][n_exp][n_comp + ones] with ``sysrem_orders``) and
     ``data`` [n_inj][n_exp][n_pix] in the caller's pixel order (None when the data were not asked for).  ``grid[b]`` is
     the Cleaned that Transit.inject returns for (trials[b], scales[b])."""
 
@@ -644,10 +723,16 @@ def _check_grid_list(who, inj, trials, scales):
     return t, s
 
 
-def _check_sysrem_args(who, inj, n_comp, n_iter, ones, highpass):
+def _check_sysrem_args(who, inj, n_comp, n_iter, ones, highpass, sysrem_orders=None):
     """The refusals of Transit.clean / Transit.inject that need no device: (n_comp, n_iter, ones) as integers."""
     if not isinstance(inj, Injection):
         raise TypeError("%s: inj must be an observation.Injection" % who)
+    if sysrem_orders is not None:
+        if not isinstance(sysrem_orders, Orders):
+            raise TypeError("%s: sysrem_orders must be an observation.Orders" % who)
+        if sysrem_orders.exposures_key != inj.exposures_key:
+            raise ValueError("%s: the Orders of sysrem_orders were made for other exposures (another table, pixels or "
+                             "data)" % who)
     if highpass is not None:
         if not isinstance(highpass, HighPass):
             raise TypeError("%s: highpass must be an observation.HighPass" % who)
