@@ -8,13 +8,14 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["csrc/prom_api.hip", "csrc/prom_api_transit.hip", "csrc/prom_api_observe.hip", "csrc/prom_api_expose.hip",
+           "csrc/prom_api_inject.hip",
            "csrc/prom_segments.hip", "csrc/prom_window.hip",
            "csrc/prom_transit.hip", "csrc/prom_fn.hip", "csrc/prom_mol.hip", "csrc/prom_tcurve.hip", "csrc/prom_rm.hip",
            "csrc/prom_sigma.hip", "csrc/prom_tw.hip",
            "csrc/prom_observe.hip", "csrc/prom_vmap.hip", "csrc/prom_expose.hip", "csrc/prom_detrend.hip",
            "csrc/prom_highpass.hip", "csrc/prom_median.hip", "csrc/prom_orders.hip", "csrc/prom_broaden.hip", "csrc/prom_sysrem.hip",
            "csrc/prom_filter.hip"]
-HEADERS = ["../include/prom_hip.h", "csrc/prom_internal.h", "csrc/prom_api_shared.h", "csrc/prom_device.h",
+HEADERS = ["../include/prom_hip.h", "csrc/prom_internal.h", "csrc/prom_api_shared.h", "csrc/prom_api_chain.h", "csrc/prom_device.h",
            "csrc/prom_tc.h", "csrc/tc_phase.h", "csrc/tw_index.h", "csrc/tw_stage.h",
            "csrc/obs_index.h", "csrc/vmap_index.h", "csrc/expose_index.h", "csrc/detrend_index.h",
            "csrc/highpass_index.h", "csrc/median_index.h", "csrc/order_index.h", "csrc/broaden_index.h", "csrc/sysrem_index.h",

@@ -4,13 +4,13 @@
 // sub-batches under a byte cap.
 //
 // Plain inline functions shared by the kernels (prom_sysrem.hip, prom_filter.hip), the C-ABI layer
-// (prom_api_expose.hip) and the host harness (tests/helpers/grid_host.cpp, tests/test_inject_grid_cpu.py), which walks
+// (prom_api_inject.hip) and the host harness (tests/helpers/grid_host.cpp, tests/test_inject_grid_cpu.py), which walks
 // every thread of every batched kernel with this text.  The arithmetic of an entry is not here: it stays sy_* of
 // sysrem_index.h, fw_* of filter_index.h and dt_* of detrend_index.h, so the bits of injection b are the single call's.
 //
 // The layout: a per-injection buffer of the single call with n entries becomes [B][n], injection b's slice first to
 // last, so every kernel of the single call runs on b's slice with its own index functions after one offset, and the
-// single call is the batch of one (offset 0).  The injection is blockIdx.y of every batched launch.  The two buffers
+// single call is the batch of one (offset 0): the C-ABI layer runs it as a list of one.  The injection is blockIdx.y of every batched launch.  The two buffers
 // k_expose writes and reads keep its layout with the injection in the trial's place: Fj[e][b][tap] and model[e][b][p].
 // The flags are [B][kGrFlags]: a component that ends sets flag `col` of its own row and nothing else.
 #pragma once

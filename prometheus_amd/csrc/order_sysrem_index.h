@@ -7,7 +7,7 @@
 //                           ivar[e][perm[first_s + i]] for i < n_s, w = 0 and r = +0 beyond
 //   k_sysrem_finish_orders  item y, exposure e, position i < n_s: out[b][e][perm[first_s + i]]
 //
-// Plain inline functions shared by the kernels (prom_sysrem.hip), the C-ABI layer (prom_api_expose.hip) and the host
+// Plain inline functions shared by the kernels (prom_sysrem.hip), the C-ABI layer (prom_api_inject.hip) and the host
 // harness (tests/helpers/order_sysrem_host.cpp, tests/test_sysrem_orders_cpu.py), which walks every thread of the two
 // kernels with this text.  The arithmetic of an entry stays sy_* of sysrem_index.h.
 //

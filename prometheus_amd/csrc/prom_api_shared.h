@@ -1,6 +1,7 @@
 // What the translation units of the C-ABI layer share (prom_api.hip, prom_api_transit.hip, prom_api_observe.hip,
-// prom_api_expose.hip): the guard of every entry, the copies, the checks of tables and density models, and the few
-// checks the observation entries make in the same words.  Host code only.
+// prom_api_expose.hip, prom_api_inject.hip): the guard of every entry, the copies, the checks of tables and density
+// models, the few checks the observation entries make in the same words, and the source of an entry's spectrum as a
+// value.  Host code only.
 #pragma once
 
 #include <algorithm>
@@ -133,6 +134,37 @@ TransitArgs transit_args(prom_ctx* ctx, const char* who, int32_t n_orb, const ch
   if (!tr.ran) throw Error(PROM_E_STATE, std::string(who) + ": no completed run");
   if (n_orb != tr.n_orb) throw Error(PROM_E_STATE, std::string(who) + ": " + what + " has another n_orb");
   return TransitArgs{ctx->streams[tr.last], tr.wav.as<double>(), transit_R(ctx), tr.n_wav};
+}
+
+// where an entry's spectrum comes from: none (prom_sysrem_clean), the last run's (a prom_transit_* entry) or the
+// caller's (n_orb, n_wav, wav, R) (a prom_spectrum_* entry).  `source` is SyDev's last_source of the call.  A family
+// resolves it to TransitArgs with its own buffers (ex_args, sy_args), through the two functions above
+struct Spectrum {
+  int32_t source;   // 1: none, 2: the last run's, 3: the caller's
+  int32_t n_orb;
+  int64_t n_wav;
+  const double *wav, *R;
+};
+constexpr Spectrum kNoSpectrum{1, 0, 0, nullptr, nullptr}, kLastRun{2, 0, 0, nullptr, nullptr};
+Spectrum callers(int32_t n_orb, int64_t n_wav, const double* wav, const double* R) {
+  return Spectrum{3, n_orb, n_wav, wav, R};
+}
+
+// ---- the exposure table, as the exposures' and the injections' entries ask for it ------------------------------------
+constexpr int64_t kMaxGrid = ((int64_t)1 << 31) - 1;   // workgroups of one launch
+
+bool table_present(const prom_ctx* ctx) { return ctx->ex.set && ctx->obs.set && ctx->obs.n_orb == ctx->ex.n_orb; }
+
+void expose_check(prom_ctx* ctx, const char* who) {
+  if (!table_present(ctx))
+    throw Error(PROM_E_STATE, std::string(who) + ": no exposure table on the context (prom_expose_set; a later "
+                                                 "prom_observe_set or a prom_transit_set with another n_orb drops it)");
+}
+
+// the sets' own test: the table they belong to is there
+void table_check(const prom_ctx* ctx, const char* who) {
+  if (!table_present(ctx))
+    throw Error(PROM_E_STATE, std::string(who) + ": no exposure table on the context (prom_expose_set)");
 }
 
 // "no pixel: every moment 0" for n (row, trial) pairs

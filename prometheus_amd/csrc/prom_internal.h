@@ -513,9 +513,11 @@ struct SyDev {
   DevBuf D, out;                          // [n_exp][n_pix]: injected (and high-passed) data, cleaned data
   DevBuf r, w;                            // [n_exp][sy_pitch(n_pix)]: residuals and weights
   DevBuf a, ended, part, U;               // [n_exp], int32 [kSyMaxComp + 1], [n_exp][tiles] {num, den}, [n_exp][cols]
-  DevBuf trial, scale;                    // an injection grid's list (int32, double); its sub-batches keep [B][...] of
-                                          // D .. U above and Fj [n_exp][B][n_tap], model [n_exp][B][n_pix]
-  DevBuf Fj, model, q, epart;             // one trial: factors [n_exp][n_tap], model [n_exp][n_pix], q [n_wav], k_expose's records
+  DevBuf trial, scale;                    // the list of injections (int32, double): a grid's, or a single call's one entry;
+                                          // a sub-batch of B keeps [B][...] of D .. U above (a single call: B = 1) and ...
+  DevBuf Fj, model, q, epart;             // ... factors [n_exp][B][n_tap], model [n_exp][B][n_pix], q [n_wav], k_expose's records
+  int32_t one_trial = 0;                  // the host side of a single call's list: it outlives the copies to trial, scale
+  double one_scale = 0.0;
   DevBuf wav, R;                          // prom_spectrum_inject's copies of the caller's spectrum
   // the last call, for prom_sysrem_kernel_ms to repeat (source 0: none yet, 1: clean, 2: transit, 3: spectrum)
   int32_t last_source = 0, last_trial = 0, last_highpass = 0, last_n_comp = 0, last_n_iter = 0, last_ones = 0;
@@ -732,19 +734,16 @@ struct BrRec;
 struct BrKern;
 void launch_broaden(hipStream_t s, const double* wav, const double* q, const double* R, int32_t n_wav, int32_t n_orb,
                     const BrRec* rec, const BrKern& kern, double* Rb, hipEvent_t ev0, hipEvent_t ev1);
-// injection and SYSREM (prom_sysrem.hip): one trial's factors out of F[n_exp][n_trial][n_tap]; D from raw and the
-// one-trial model; the whole of SYSREM on D[n_exp][n_pix] with the work buffers r, w (pitched), a, ended, part:
+// SYSREM (prom_sysrem.hip): the whole of it on D[n_exp][n_pix] with the work buffers r, w (pitched), a, ended, part:
 // U[n_exp][n_comp + ones] and out[n_exp][n_pix], nothing waits
-void launch_sysrem_gather(hipStream_t s, const double* F, double* Fj, int32_t n_exp, int32_t n_trial, int32_t n_tap,
-                          int32_t j);
-void launch_inject(hipStream_t s, const double* raw, const double* model, double scale, double* D, int64_t n);
 void launch_sysrem(hipStream_t s, const double* D, const double* ivar, double* r, double* w, double* a, int32_t* ended,
                    double* part, double* U, double* out, int32_t n_exp, int32_t n_pix, int32_t n_comp, int32_t n_iter,
                    int32_t ones, int32_t n_inj = 1);
 // the injection grids (prom_sysrem.hip, grid_index.h): launch_sysrem with n_inj injections works on [n_inj][...] of
 // every buffer but ivar (ended: int32 [n_inj][kGrFlags]) in the same number of launches; before it the factors of the
 // listed trials as a table of n_inj trials, Fj[n_exp][n_inj][n_tap], and D[n_inj][n_exp][n_pix] from raw, the model
-// [n_exp][n_inj][n_pix] of that table and scale[n_inj] (trial and scale on the device)
+// [n_exp][n_inj][n_pix] of that table and scale[n_inj] (trial and scale on the device).  A single inject call is the
+// list of one
 void launch_gather_grid(hipStream_t s, const double* F, double* Fj, const int32_t* trial, int32_t n_exp, int32_t n_trial,
                         int32_t n_tap, int32_t n_inj);
 void launch_inject_grid(hipStream_t s, const double* raw, const double* model, const double* scale, double* D,

@@ -2,10 +2,10 @@
 // prom_spectrum_inject): a trial's model multiplied into the raw exposures, the resident high-pass along each order,
 // then the alternating least-squares fits of SYSREM, component by component.  Definitions in prom_hip.h.
 //
-//   k_sysrem_gather  Fj[e][tap] = F[e][j][tap]: the factors of one trial, so that ...
-//   k_expose         (prom_expose.hip, unchanged) ... forms model[e][p] of that trial alone, as a table of one trial
-//   k_inject         D[e][p] from raw and the one-trial model
-//   k_highpass       (prom_highpass.hip, unchanged, on request) D in place, as a model of one trial
+//   k_gather_grid    Fj[e][b][tap] = F[e][trial[b]][tap]: the factors of the listed trials, so that ...
+//   k_expose         (prom_expose.hip, unchanged) ... forms model[e][b][p] of those trials alone, with B in n_trial's place
+//   k_inject_grid    D[b][e][p] from raw[e][p], model[e][b][p] and scale[b]
+//   k_highpass       (prom_highpass.hip, unchanged, on request) D in place, as a model of B trials
 //   k_sysrem_prep    w[e][p] and r[e][p] of the pitched work buffers from D and ivar; the padding gets w = 0, r = +0
 //   k_sysrem_fill    a[e] and U[e][col] = one value (a component's first a; the column of ones)
 //   k_sysrem_step    a workgroup (one wave) owns a tile of kSyTile pixel columns and keeps c_p in registers: it walks
@@ -23,10 +23,10 @@
 //
 // The injection grids (prom_*_inject_grid / prom_*_recover_grid) run the same five SYSREM kernels: blockIdx.y is the
 // injection b, every per-injection buffer is [B][the single call's], and a kernel moves its pointers to b's slice
-// (grid_index.h) before it does what it did; the single call is the batch of one.  A component that ends sets flag
-// `col` of b's own row of `ended`, so it stops b's later launches and nobody else's.  Two kernels are the grid's own:
-//   k_gather_grid    Fj[e][b][tap] = F[e][trial[b]][tap]: k_expose then runs unchanged with B in n_trial's place
-//   k_inject_grid    D[b][e][p] from raw[e][p], model[e][b][p] and scale[b]
+// (grid_index.h) before it does what it did.  The single call is the batch of one, literally: the C-ABI layer has one
+// runner (prom_api_inject.hip, inject_steps), and a single call gives it a list of one entry, so every kernel here is one
+// batched text with B = 1 and offset 0.  A component that ends sets flag `col` of b's own row of `ended`, so it stops
+// b's later launches and nobody else's.
 //
 // SYSREM per order (prom_sysrem_clean_orders, prom_*_inject_orders, prom_*_inject_grid_orders): an order is one more
 // batch item.  Item y = b n_seg + s of the work buffers is order s of injection b, n_max = max n_s wide
@@ -47,22 +47,6 @@ static_assert(kSyRowsBlock % 64 == 0 && kSyRowsBlock <= 1024, "k_sysrem_rows: wh
 struct alignas(kSyVec * 8) SyVecD {
   double x[kSyVec];
 };
-
-__global__ void __launch_bounds__(kSyFlatBlock) k_sysrem_gather(const double* __restrict__ F, double* __restrict__ Fj,
-                                                                int32_t n_exp, int32_t n_trial, int32_t n_tap,
-                                                                int32_t j) {
-  const int64_t i = (int64_t)blockIdx.x * kSyFlatBlock + threadIdx.x;
-  if (i >= (int64_t)n_exp * n_tap) return;
-  const int32_t e = (int32_t)(i / n_tap), tap = (int32_t)(i % n_tap);
-  Fj[ex_tap(e, tap, n_tap)] = F[ex_factor(e, j, tap, n_trial, n_tap)];
-}
-
-__global__ void __launch_bounds__(kSyFlatBlock) k_inject(const double* __restrict__ raw, const double* __restrict__ model,
-                                                         double scale, double* __restrict__ D, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * kSyFlatBlock + threadIdx.x;
-  if (i >= n) return;
-  D[i] = sy_inject(raw[i], model[i], scale);
-}
 
 __global__ void __launch_bounds__(kSyFlatBlock) k_gather_grid(const double* __restrict__ F, double* __restrict__ Fj,
                                                               const int32_t* __restrict__ trial, int32_t n_exp,
@@ -296,20 +280,6 @@ static uint32_t flat_grid(int64_t n, const char* who) {
   const int64_t wgs = sy_flat_workgroups(n);
   if (wgs > (((int64_t)1 << 31) - 1)) throw Error(PROM_E_ARG, std::string(who) + ": too many entries for one launch");
   return (uint32_t)wgs;
-}
-
-void launch_sysrem_gather(hipStream_t s, const double* F, double* Fj, int32_t n_exp, int32_t n_trial, int32_t n_tap,
-                          int32_t j) {
-  if (n_exp <= 0 || n_tap <= 0) return;
-  hipLaunchKernelGGL(k_sysrem_gather, dim3(flat_grid((int64_t)n_exp * n_tap, "k_sysrem_gather")), dim3(kSyFlatBlock), 0,
-                     s, F, Fj, n_exp, n_trial, n_tap, j);
-  PROM_HIP(hipGetLastError());
-}
-
-void launch_inject(hipStream_t s, const double* raw, const double* model, double scale, double* D, int64_t n) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_inject, dim3(flat_grid(n, "k_inject")), dim3(kSyFlatBlock), 0, s, raw, model, scale, D, n);
-  PROM_HIP(hipGetLastError());
 }
 
 void launch_gather_grid(hipStream_t s, const double* F, double* Fj, const int32_t* trial, int32_t n_exp, int32_t n_trial,
